@@ -15,6 +15,11 @@ Launch modes (reference main.py:80-85 launches its ranks itself with mp.spawn; s
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
     python bench.py --sweep 1,2,4,8                                               # one fresh rank group per N,
                                                                                   # + scaling-efficiency summary
+A plain run sets up, warms up, times the K steps and prints the result line: nothing else.  ``--full`` adds the
+second, fp32 (reference precision) timing of bf16 runs to the same invocation (``fp32_*`` keys; ``--no-fp32`` drops
+it again).  ``--dump-outputs DIR`` writes what the last timed step left behind -- the model's ``state_dict()``
+(parameters, BN running statistics) and the accumulated loss -- as ``DIR/<name>.npy`` (float32 / float64) from
+rank 0; data, sample order and initial weights are seeded, so two builds can be compared array for array.
 The parent of a self-launch never touches the GPU (ranks are spawned before any HIP call).
 DCA_BENCH_SHARE_GPU=1 (rehearsal on a 1-GPU box): every rank on GPU 0, gloo process group, xGMI all-reduce.
 """
@@ -61,8 +66,14 @@ def _args(argv=None):
                          "(protocol cost on one device; not the headline configuration)")
     ap.add_argument("--sweep", default=None, metavar="N1,N2,..",
                     help="run each N in a fresh spawned rank group; print per-N lines and a scaling summary")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: for bf16 runs the second, fp32 "
+                         "(reference precision) timing in the same invocation")
     ap.add_argument("--no-fp32", action="store_true",
-                    help="bf16 runs: skip the second, fp32 (reference precision) timing in the same invocation")
+                    help="--full bf16 runs: skip the second, fp32 (reference precision) timing after all")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the model's state_dict and the accumulated loss as "
+                         "DIR/<name>.npy (rank 0; float32, counters and the loss float64)")
     ap.add_argument("--result-file", default=None, help=argparse.SUPPRESS)  # rank 0 -> parent (sweep)
     return ap.parse_args(argv)
 
@@ -102,8 +113,9 @@ def run_rank(a) -> dict | None:
     sampler = torch.utils.data.distributed.DistributedSampler(range(50000), num_replicas=world, rank=rank)
     order = np.resize(np.fromiter(iter(sampler), dtype=np.int32), (a.warmup + a.steps) * a.batch)
 
-    def timed(dtype: str):
-        """W warm-up + K timed steps of a fresh model / engine in `dtype`; the slowest rank's seconds."""
+    def timed(dtype: str, dump_dir=None):
+        """W warm-up + K timed steps of a fresh model / engine in `dtype`; the slowest rank's seconds.  With
+        `dump_dir` rank 0 then writes the trained state there (--dump-outputs)."""
         torch.manual_seed(1234 + rank)  # ranks init differently; the DDP wrap broadcasts rank 0's weights (CC3)
         model = NetResDeep().to(dev)
         persistent = None if a.engine == "auto" else a.engine == "persistent"
@@ -135,10 +147,19 @@ def run_rank(a) -> dict | None:
         loss_sum, nsteps = eng.read_loss()
         out = {"dt": max(p[0] for p in per_rank), "per_rank": per_rank, "loss": loss_sum / max(nsteps, 1),
                "ok": bool(np.isfinite(loss_sum)), "engine": eng.kind_name, "comm": trainer.comm}
+        if dump_dir and rank == 0:
+            # the engine trains the module's own parameters and BN buffers in place (they are views of its flat
+            # buffer), so after the sync above state_dict() is what the last timed step left
+            os.makedirs(dump_dir, exist_ok=True)
+            for name, t in model.state_dict().items():
+                arr = t.detach().cpu().numpy()
+                np.save(os.path.join(dump_dir, name + ".npy"),
+                        arr.astype(np.float32 if arr.dtype.kind == "f" else np.float64))
+            np.save(os.path.join(dump_dir, "loss_sum.npy"), np.array([loss_sum, nsteps], dtype=np.float64))
         trainer.close()
         return out
 
-    main_run = timed(a.dtype)
+    main_run = timed(a.dtype, a.dump_outputs)
     dt, per_rank, ok = main_run["dt"], main_run["per_rank"], main_run["ok"]
     value = world * a.batch * a.steps / dt
     ref = REF_EAGER_IPS_PER_GPU.get(a.dtype)
@@ -171,7 +192,7 @@ def run_rank(a) -> dict | None:
         "loss_finite": ok,
         "mean_loss": main_run["loss"],
     }
-    if a.dtype == "bf16" and not a.no_fp32:
+    if a.full and a.dtype == "bf16" and not a.no_fp32:
         # the reference's precision, timed in the same invocation (same steps / warm-up / ranks).  The sliced
         # engine's fp32 is "3xbf16": every MFMA operand split into bf16 hi + lo, products hi*hi + hi*lo + lo*hi,
         # fp32 accumulation / BatchNorm / loss / SGD (measured against the fp32 oracle: tests/test_engine_gpu.py)

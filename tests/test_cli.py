@@ -143,3 +143,13 @@ def test_bench_sets_dmabuf_ipc_mode():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "1"
     r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "1", (r.stdout, r.stderr[-2000:])
+
+
+def test_bench_plain_run_options():
+    """A plain run measures the headline figure only: the second (fp32) timing is opt-in (--full) and nothing is
+    written unless --dump-outputs names a directory."""
+    import bench
+    a = bench._args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench._args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and not a.no_fp32

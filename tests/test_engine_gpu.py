@@ -310,14 +310,28 @@ def test_full_device_engine_choice(gpu):
         tr.close()
 
 
-def test_bench_contract(gpu):
-    r = _run(["bench.py", "--steps", "20", "--warmup", "5"])
+def test_bench_contract(gpu, tmp_path):
+    """A plain run: the result line, only the headline (bf16) timing, and with --dump-outputs the trained state."""
+    import numpy as np
+    from distributeddataparallel_cifar10_amd.runtime.engine import LAYOUT
+    out = tmp_path / "out"
+    r = _run(["bench.py", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config"):
         assert k in rec, k
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and rec["loss_finite"]
+    assert rec["steps"] == 20 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    assert not any(k.startswith("fp32_") for k in rec), rec  # the second timing is behind --full
+    for name, (_, shape) in LAYOUT.items():
+        arr = np.load(out / f"{name}.npy")
+        assert arr.dtype == np.float32 and arr.shape == shape and np.isfinite(arr).all(), name
+    for name in ("running_mean", "running_var"):
+        arr = np.load(out / f"resblocks.0.batch_norm.{name}.npy")
+        assert arr.dtype == np.float32 and arr.shape == (32,) and np.isfinite(arr).all(), name
+    loss_sum, nsteps = np.load(out / "loss_sum.npy")
+    assert nsteps == 25 and abs(loss_sum / nsteps - rec["mean_loss"]) < 1e-9
 
 
 @pytest.mark.parametrize("persistent", [True, False])

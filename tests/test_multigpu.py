@@ -71,9 +71,9 @@ def _check_bench_line(out, n, allreduce=None, batch=32):
 @pytest.mark.skipif(_ngpu() < 2, reason="needs >= 2 GPUs (one rank per device)")
 def test_bench_driver_command(gpu):
     """The driver's command verbatim: ``python bench.py --gpus N --steps K --warmup W`` (bench.py spawns the N
-    ranks itself); bf16 value plus the fp32 (reference precision) timing of the same invocation."""
+    ranks itself); with ``--full`` the bf16 value plus the fp32 (reference precision) timing of the same invocation."""
     n = min(_ngpu(), 8)
-    lines = _bench(["bench.py", "--gpus", str(n), "--steps", "48", "--warmup", "16"])
+    lines = _bench(["bench.py", "--gpus", str(n), "--steps", "48", "--warmup", "16", "--full"])
     assert len(lines) == 1, lines
     _check_bench_line(lines[0], n)
 
@@ -85,7 +85,7 @@ def test_bench_torchrun_one_rank_per_gpu(gpu, port, allreduce):
     n = min(_ngpu(), 8)
     lines = _bench(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
                     "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", str(n), "--steps", "48",
-                    "--warmup", "16", "--allreduce", allreduce])
+                    "--warmup", "16", "--allreduce", allreduce, "--full"])
     assert len(lines) == 1, lines
     _check_bench_line(lines[0], n, allreduce)
 
@@ -131,7 +131,8 @@ def test_bench_driver_command_shared_gpu(gpu):
     """``python bench.py --gpus 2`` with both ranks on GPU 0: self-launch, gloo rendezvous, the engine's xGMI
     gradient exchange between the ranks, slowest-rank timing and the fp32 second timing.  Per-rank batch 16: two
     batch-32 grids (2 x 128 step workgroups) would fill the device exactly, which the co-residency rule refuses."""
-    lines = _bench(["bench.py", "--gpus", "2", "--batch", "16", "--steps", "32", "--warmup", "8"], shared=True)
+    lines = _bench(["bench.py", "--gpus", "2", "--batch", "16", "--steps", "32", "--warmup", "8", "--full"],
+                   shared=True)
     assert len(lines) == 1, lines
     _check_bench_line(lines[0], 2, "xgmi", batch=16)
 
@@ -150,8 +151,8 @@ def test_bench_driver_command_shared_gpu_8_ranks(gpu):
     budget exactly and a rank's BN exchange once timed out while a peer's kernels held CUs): self-launch of 8 ranks,
     the engine's xGMI exchange with 8 peers in every gradient segment, CC4 through 8 ranks, slowest-rank timing,
     fp32 second timing."""
-    lines = _bench(["bench.py", "--gpus", "8", "--batch", "4", "--steps", "32", "--warmup", "8"], shared=True,
-                   timeout=600)
+    lines = _bench(["bench.py", "--gpus", "8", "--batch", "4", "--steps", "32", "--warmup", "8", "--full"],
+                   shared=True, timeout=600)
     assert len(lines) == 1, lines
     out = lines[0]
     assert out["n_gpus"] == 8 and out["allreduce"] == "xgmi" and out["loss_finite"] and out["fp32_loss_finite"]

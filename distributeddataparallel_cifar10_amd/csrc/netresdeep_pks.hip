@@ -73,12 +73,26 @@ struct Plan {
   static constexpr int O_STAT = O_CRED + 2 * NW * 64 * 4;  // [10][32] f32x4: mean, invstd, BN scale, shift of every
                                                          // block (one 16-B LDS read per channel in the backward)
   static constexpr int O_MISC = O_STAT + 5120;           // [1280] f32 step constants (layout: k_pks_step)
-  static constexpr int O_U = O_MISC + 5120;              // phase union
+  // stem-backward inputs made in the forward, never aliased: the three column-shifted copies of the normalised
+  // input (built from XIN during forward block 0's exchange) and every thread's packed stem pool codes
+  static constexpr int XSR = 2 * RS + 2;                 // input rows 8s-1 .. 8s+8
+  static constexpr int XS_S = 40;
+  static constexpr int XS_PL = 9 * XSR * XS_S * 2;       // [3 kw][3 ci][XSR][XS_S] shifted input copies
+  static constexpr int O_XS = O_MISC + 5120;
+  static constexpr int O_CODE = O_XS + NP * XS_PL;       // [NTH] u32: 4 pool codes of the thread's 4 pixels
+  static constexpr int O_U = O_CODE + NTH * 4;           // trunk regions + phase union
+  // RES (bf16: LDS to spare at one workgroup per CU): the dgrad weights are resident beside the forward ones (both
+  // staged at kernel start) and XR / dyT / xT are never aliased, so they are zeroed once, in the stem; one phase
+  // union after them (from U_PH) holds stem XIN / X0 / SCODE | head X10 / W1 / PCODE / DP / PL / HP | stem-backward
+  // dsT / SRED.  !RES (fp32, two planes of everything): the dgrad weights replace the forward ones in WT after
+  // block 9, the head overlays XR / dyT / xT (zeroed again at the backward's entry), dsT / SRED overlay WT / XR.
+  static constexpr bool RES = P == 0;
   // trunk, forward and backward
   static constexpr int WT_PL = 288 * RB;                 // conv weight records [tap][co | ci] x 32
   static constexpr int U_WT = 0;
+  static constexpr int U_WTD = RES ? U_WT + NP * WT_PL : U_WT;  // dgrad weights
   static constexpr int XR_PL = (RS + 2) * 18 * RB;       // conv input records, rows -1..RS, cols -1..16
-  static constexpr int U_XR = U_WT + NP * WT_PL;
+  static constexpr int U_XR = U_WTD + NP * WT_PL;
   static constexpr int U_XR_END = U_XR + NP * XR_PL;
   static constexpr int DYT_S = RS * 16 + 8;              // dy, channel-major (wgrad A operand)
   static constexpr int DYT_PL = 32 * DYT_S * 2;
@@ -87,45 +101,56 @@ struct Plan {
   static constexpr int XT_PL = 3 * 32 * XT_S * 2;
   static constexpr int U_XT = U_DYT + NP * DYT_PL;
   static constexpr int BWD_END = U_XT + NP * XT_PL;
-  // stem (start of the step; WT and XR live)
+  static constexpr int U_PH = BWD_END;                         // RES: the phase union
+  // stem (start of the step; WT and XR live; XIN stays until forward block 0 has built xs from it)
   static constexpr int XIN_ROWS = 2 * RS + 6, XIN_COLS = 34;  // input rows 8s-3 .. 8s+10, cols -1..32
   static constexpr int XIN_PL = XIN_ROWS * XIN_COLS * 8;      // NHWC4 bf16 pixels
-  static constexpr int U_XIN = U_XR_END;
+  static constexpr int U_XIN = RES ? U_PH : U_XR_END;
   static constexpr int X0S = 36;
   static constexpr int U_X0 = U_XIN + NP * XIN_PL;             // [RS + 2][16][X0S] f32 pooled stem output
   static constexpr int U_SCODE = U_X0 + (RS + 2) * 16 * X0S * 4;  // [RS][16][32] u8 stem pool codes
   static constexpr int STEM_END = U_SCODE + RS * 16 * 32;
-  // head (WT live -- it receives the dgrad weights meanwhile -- XR / dyT / xT free)
+  // head (RES: in the phase union, over the stem's regions; else WT live -- it receives the dgrad weights
+  // meanwhile -- and XR / dyT / xT free)
   static constexpr int X10S = 33;
-  static constexpr int U_X10 = U_XR;                           // [RS][16][X10S] f32
+  static constexpr int U_X10 = RES ? U_PH : U_XR;              // [RS][16][X10S] f32
   static constexpr int X10_BYTES = RS * 16 * X10S * 4;
   static constexpr int W1S = P == 1 ? 516 : 520;               // fc1 slice row stride (elements)
   static constexpr int W1_BYTES = 32 * W1S * (P == 1 ? 4 : 2); // [32 rows][512 local features] (f32 | bf16)
-  static constexpr int U_W1 = (cmax(U_XR_END, U_X10 + X10_BYTES) + 15) / 16 * 16;
+  static constexpr int U_W1 = (cmax(RES ? U_PH : U_XR_END, U_X10 + X10_BYTES) + 15) / 16 * 16;
   static constexpr int U_PCODE = U_W1 + W1_BYTES;              // [512] u8 pool argmax
   static constexpr int U_DP = U_PCODE + 512;                   // [512] f32 dL/dpooled
   static constexpr int U_PL = U_DP + 2048;                     // [512] f32 pooled features
   static constexpr int U_HP = U_PL + 2048;                     // [32] fc1 partials | [32, 64) dh
   static constexpr int HEAD_END = U_HP + 256;
-  // stem backward (WT / XR free)
+  // stem backward (RES: in the phase union, over the head's regions; else over WT / XR, free by then)
   static constexpr int DSP = 2 * RS * 32 + 8;                  // d(conv1 out), channel-major, own conv rows
   static constexpr int DST_PL = 32 * DSP * 2;
-  static constexpr int U_DST = 0;
-  static constexpr int XSR = 2 * RS + 2;                       // input rows 8s-1 .. 8s+8
-  static constexpr int XS_S = 40;
-  static constexpr int XS_PL = 9 * XSR * XS_S * 2;             // [3 kw][3 ci][XSR][XS_S] shifted input copies
-  static constexpr int U_XS = U_DST + NP * DST_PL;
-  static constexpr int U_SRED = U_XS + NP * XS_PL;             // [NW][64][4] f32 stem-wgrad partials (written
-                                                               // after the barrier that retires the last wgrad)
+  static constexpr int U_DST = RES ? U_PH : 0;
+  static constexpr int U_SRED = U_DST + NP * DST_PL;           // [NW][64][4] f32 stem-wgrad partials
   static constexpr int SBWD_END = U_SRED + NW * 64 * 16;
   static constexpr int UNION = cmax(cmax(BWD_END, STEM_END), cmax(HEAD_END, SBWD_END));
   static constexpr int TOTAL = O_U + UNION;
 };
-static_assert(Plan<1>::TOTAL <= 160 * 1024, "LDS budget");
-static_assert(Plan<0>::U_W1 >= Plan<0>::U_X10 + Plan<0>::X10_BYTES, "x10 clear of the fc1 slice");
-// dsT / xs are written while other waves may still run the last wgrad (dyT / xT); SRED only after the barrier
-static_assert(Plan<0>::U_SRED <= Plan<0>::U_DYT, "stem-backward staging clear of dyT / xT (last wgrad)");
+static_assert(Plan<0>::TOTAL <= 160 * 1024 && Plan<1>::TOTAL <= 160 * 1024, "LDS budget");
+static_assert(Plan<0>::TOTAL == 138528 && Plan<1>::TOTAL == 152384, "the documented LDS sizes");
+static_assert(Plan<0>::TOTAL > 80 * 1024 && Plan<1>::TOTAL > 80 * 1024, "one step workgroup per CU by LDS alone");
+static_assert(Plan<0>::O_U % 16 == 0 && Plan<1>::O_U % 16 == 0 && Plan<0>::U_PH % 16 == 0, "16-byte aligned regions");
+static_assert(Plan<0>::U_W1 >= Plan<0>::U_X10 + Plan<0>::X10_BYTES && Plan<1>::U_W1 >= Plan<1>::U_X10 + Plan<1>::X10_BYTES,
+              "x10 clear of the fc1 slice");
+// RES: the phase union starts past everything the trunk keeps (WT, WTd, XR, dyT, xT), so the head never touches the
+// backward's zeroed borders and the stem backward's dsT / SRED stay clear of the last wgrad's dyT / xT
+static_assert(Plan<0>::U_XIN >= Plan<0>::BWD_END && Plan<0>::U_X10 >= Plan<0>::BWD_END &&
+                  Plan<0>::U_DST >= Plan<0>::BWD_END && Plan<0>::U_WTD >= Plan<0>::U_WT + Plan<0>::WT_PL &&
+                  Plan<0>::U_XR >= Plan<0>::U_WTD + Plan<0>::WT_PL,
+              "bf16: trunk regions never aliased");
+// XIN is read (xs build) in forward block 0; the first writer of the head's regions is the fc1 DMA after block
+// NBLK - 4's exchange (x10 only in the head): XIN may overlay either, X0 / SCODE are dead once the stem ends
+static_assert(Plan<0>::U_XIN + Plan<0>::XIN_PL <= Plan<0>::U_W1 && Plan<1>::U_XIN >= Plan<1>::U_XR_END,
+              "XIN: under x10 only (bf16) / clear of XR, which the forward rewrites (fp32)");
+// !RES: dsT is written while other waves may still run the last wgrad (dyT / xT); SRED only after a barrier
 static_assert(Plan<1>::U_SRED <= Plan<1>::U_DYT, "stem-backward staging clear of dyT / xT (last wgrad)");
+static_assert(Plan<1>::SBWD_END <= Plan<1>::U_DYT, "fp32: SRED clear of dyT / xT too");
 
 // ---- helpers ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -521,6 +546,33 @@ __device__ __forceinline__ void xr_row(char* XR, int xrow, int q, int ch, const 
   using PL = Plan<P>;
 #pragma unroll
   for (int i = 0; i < 4; ++i) st1r<P>(XR, PL::XR_PL, xrow * 18 + 4 * q + i + 1, ch, v[i]);
+}
+
+// The stem backward's B operand: three column-shifted copies of the normalised input rows 8s-1 .. 8s+8 (copy kw holds
+// x[col + kw - 1] at col), gathered from the bf16 pixels the stem staged in XIN (rows 8s-3 .. 8s+10 with zero columns
+// -1 and 32 and zero rows outside the image: the borders come along; the same bits as rounding norm_px again).
+// Thread t < 240: channel t / 80, row (t % 80) >> 3, columns 4 (t & 7) .. + 3 of every copy.
+template <int P>
+__device__ __forceinline__ void xs_build(const uint2* xin4, unsigned short* xs, int t) {
+  using PL = Plan<P>;
+  if (t < 240) {
+    const int ci = t / 80, rem = t % 80, xr_ = rem >> 3, x0 = 4 * (rem & 7);
+#pragma unroll
+    for (int p = 0; p <= P; ++p) {
+      const uint2* src = xin4 + p * (PL::XIN_PL / 8) + (xr_ + 2) * PL::XIN_COLS + x0;  // image columns x0-1 .. x0+4
+      unsigned v[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        const uint2 px = src[k];
+        v[k] = ci == 2 ? (px.y & 0xffffu) : (ci == 1 ? px.x >> 16 : (px.x & 0xffffu));
+      }
+      unsigned short* base = xs + p * (PL::XS_PL / 2);
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw)
+        *(uint2*)(base + ((kw * 3 + ci) * PL::XSR + xr_) * PL::XS_S + x0) =
+            uint2{v[kw] | (v[kw + 1] << 16), v[kw + 2] | (v[kw + 3] << 16)};
+    }
+  }
 }
 
 // weight staging: the NP planes (hi, lo) of one conv weight, stored in global memory in the LDS record layout
@@ -1178,7 +1230,10 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
   float* misc = (float*)(smem + PL::O_MISC);
   char* U = smem + PL::O_U;
   char* WT = U + PL::U_WT;
+  char* WTD = U + PL::U_WTD;  // dgrad weights: resident (RES) or WT itself, restaged after forward block 9
   char* XR = U + PL::U_XR;
+  unsigned short* xs = (unsigned short*)(smem + PL::O_XS);
+  unsigned* codes = (unsigned*)(smem + PL::O_CODE);
   const int epoch = step_epoch(pa, ra);
   const int par = epoch & 1;
   const bool prev = PRO && ra_prev(ra);  // the previous step's gradient segments are applied in this launch
@@ -1241,9 +1296,13 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
       kc[m] = prev ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *src;
     }
     if constexpr (!PRO) image_loads();  // (after the constants: the round-4 order)
-    // forward trunk weights, records [tap][co] x ci (hi, lo)
+    // forward trunk weights, records [tap][co] x ci (hi, lo); RES: the dgrad weights too, records [8 - tap][ci] x co
     if (prev) wt_copy_sc1<P>(WT, pkw);
     else wt_dma<P>(WT, pkw, wv, lane);
+    if constexpr (PL::RES) {
+      if (prev) wt_copy_sc1<P>(WTD, pkw + PKW_DGRAD);
+      else wt_dma<P>(WTD, pkw + PKW_DGRAD, wv, lane);
+    }
     uint2 bwr[P + 1][2][3];        // conv1 B fragments: lane (co = 16h + c, k-group q) of MFMA m
 #pragma unroll
     for (int p = 0; p <= P; ++p)
@@ -1290,6 +1349,11 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
       if constexpr (P == 1) xin4[PL::XIN_PL / 8 + px] = uint2{0u, 0u};
     }
     for (int idx = t; idx < PL::NP * PL::XR_PL / 16; idx += NTH) ((uint4*)XR)[idx] = uint4{0u, 0u, 0u, 0u};
+    // RES: nothing but the trunk writes XR / xT, so their zero borders (columns -1 / 16, an edge slice's outer halo
+    // row, the shifted copies' end columns) are made here once, for the forward and the backward (dyT is written
+    // whole every block and needs none)
+    if constexpr (PL::RES)
+      for (int idx = t; idx < PL::XT_PL / 16; idx += NTH) ((uint4*)(U + PL::U_XT))[idx] = uint4{0u, 0u, 0u, 0u};
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's weight DMA has landed in LDS
     lds_barrier();
     DCA_STAMP(cx, 0, L, 2);
@@ -1362,8 +1426,7 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
       if (halo) xo[i] = x0i[(hxrow * 16 + 4 * q + i) * PL::X0S + ch];
       cw |= (unsigned)scl[(w * 16 + 4 * q + i) * 32 + ch] << (8 * i);
     }
-    // stem pool codes, read back by this very thread in the stem backward
-    *(unsigned*)(cx.SCODE + img8 + hh * 256 + lane * 4) = cw;
+    codes[t] = cw;  // stem pool codes, read back by this very thread in the stem backward
     if (pa.debug) st4r(cx.X + img8, hh, lane, x);
   }
   DCA_STAMP(cx, 0, L, 1);
@@ -1372,7 +1435,7 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
   // fc1 weights of this slice's 512 pooled features (local index u = ch*16 + pr*8 + pw <-> global feature
   // ch*64 + (2s + pr)*8 + pw: per row, 32 runs of 16 contiguous elements): copied into their LDS region (unused by
   // the forward) by LDS-DMA right after block 6's exchange, read by
-  // fc1 (reduction over features) and its transpose dp (reduction over rows).  The dgrad weights replace the
+  // fc1 (reduction over features) and its transpose dp (reduction over rows).  !RES: the dgrad weights replace the
   // forward ones in WT by LDS-DMA right after block 9's exchange (block 9's conv was WT's last reader).
   const float gam = misc[320 + ch], bet = misc[352 + ch];  // BN affine of this thread's channel (registers)
   bf16x8 bw[9];  // P = 0: this wave's B fragments of the conv weight (forward here, dgrad in the backward)
@@ -1402,6 +1465,8 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     if (halo) publish_row(pa, i, L, hwhich, hh, tag, y, lane);
     float yo[4];
     if (i == DCA_DETAIL_FWD) DCA_STAMP(cx, 6, L, 1);
+    // block 0, published and with nothing to do but wait: the stem backward's input copies, while XIN still stands
+    if (i == 0) xs_build<P>((const uint2*)(U + PL::U_XIN), xs, t);
     xchg_wait(pa, i, epoch, G, cred, halo, hsrc, hwhich ^ 1, hh, yo);
     if (i == DCA_DETAIL_FWD) DCA_STAMP(cx, 6, L, 2);
     st4r_wt(cx.Y + (size_t)i * B * 8192 + img8, hh, lane, y);  // this block's y for the backward (after the sweep)
@@ -1409,10 +1474,11 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     // AFTER an exchange: vmcnt is in order, so loads in flight when a sweep starts hold up its first pass (register
     // loads before the exchange + an LDS store a block later cost ~1.4 us in each of the two blocks, stamps)
     if (i == NBLK - 4) w1_dma<P>(cx, U + PL::U_W1, s, wv, lane);
-    if (i == NBLK - 1) {  // dgrad weights, records [8 - tap][ci] x co (sc1 loads: the prologue reduction wrote them)
-      if (prev) wt_copy_sc1<P>(WT, pkw + PKW_DGRAD);
-      else wt_dma<P>(WT, pkw + PKW_DGRAD, wv, lane);
-    }
+    if constexpr (!PL::RES)
+      if (i == NBLK - 1) {  // dgrad weights, records [8 - tap][ci] x co (sc1 loads: the prologue reduction wrote them)
+        if (prev) wt_copy_sc1<P>(WTD, pkw + PKW_DGRAD);
+        else wt_dma<P>(WTD, pkw + PKW_DGRAD, wv, lane);
+      }
     lds_barrier();
     if (i == DCA_DETAIL_FWD) DCA_STAMP(cx, 6, L, 3);
     if (halo) st4r_wt(pa.yh + ((size_t)(i * LMAX + L) * 2 + hwhich) * 512, hh, lane, yo);
@@ -1635,20 +1701,23 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
   // ======================= backward: 10 applications, newest first ===========================================
   unsigned short* dyT = (unsigned short*)(U + PL::U_DYT);
   unsigned short* xT = (unsigned short*)(U + PL::U_XT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dgrad weight DMA (block 9) has landed
-  lds_barrier();  // every wave is done with the head's LDS (X10 / W1 / DP overlap XR / dyT / xT)
-  if constexpr (P == 0) load_bfrag(WT, hh, lane, bw);  // dgrad B fragments
-  for (int idx = t; idx < PL::NP * PL::XR_PL / 16; idx += NTH) ((uint4*)XR)[idx] = uint4{0u, 0u, 0u, 0u};
-  for (int idx = t; idx < PL::NP * PL::XT_PL / 16; idx += NTH) ((uint4*)xT)[idx] = uint4{0u, 0u, 0u, 0u};
+  if constexpr (!PL::RES) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dgrad weight DMA (block 9) has landed
+    lds_barrier();  // every wave is done with the head's LDS (X10 / W1 / DP overlap XR / dyT / xT)
+    for (int idx = t; idx < PL::NP * PL::XR_PL / 16; idx += NTH) ((uint4*)XR)[idx] = uint4{0u, 0u, 0u, 0u};
+    for (int idx = t; idx < PL::NP * PL::XT_PL / 16; idx += NTH) ((uint4*)xT)[idx] = uint4{0u, 0u, 0u, 0u};
+    lds_barrier();
+  }
+  // RES: XR / xT kept their zero borders through the head (every other record the backward reads is rewritten by
+  // xr_row / xt_row in each block, an edge slice's outer halo row by nobody, as in the forward); the dgrad weights
+  // are in place since the stem; the head's regions are next written by the stem backward, many barriers on
+  if constexpr (P == 0) load_bfrag(WTD, hh, lane, bw);  // dgrad B fragments
   f32x4 wacc[NNT][2];
 #pragma unroll
   for (int j = 0; j < NNT; ++j) wacc[j][0] = wacc[j][1] = z4();
   float dgam = 0.f, dbet = 0.f;
-  unsigned codew = 0;  // stem-backward prefetch (during block 0)
-  unsigned imgw = 0;
-  uint4 nxt = uint4{0u, 0u, 0u, 0u};
+  uint4 nxt = uint4{0u, 0u, 0u, 0u};  // the next batch's image quarter and label (loaded during block 0)
   int nxt_lab = 0;
-  lds_barrier();
   f32x4 st4n = stat[(NBLK - 1) * 32 + ch];  // this channel's statistics of the next backward block, read ahead
 #pragma unroll 1
   for (int i = NBLK - 1; i >= 0; --i) {
@@ -1693,13 +1762,8 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     // starts holds up its first pass); they land during this block's dgrad
     if (i > 0) {  // y_{i-1}
       ld4r(cx.Y + (size_t)(i - 1) * B * 8192 + img8, hh, lane, yv);
-    } else {      // last block: what the stem backward needs (pool codes, raw input words, next batch's image)
-      codew = *(const unsigned*)(cx.SCODE + img8 + hh * 256 + lane * 4);
-      {
-        const int ci = t / 80, rem = t % 80, xr_ = rem >> 3, yimg = 8 * s - 1 + xr_;
-        const int yc = yimg < 0 ? 0 : (yimg > 31 ? 31 : yimg);
-        imgw = ((const unsigned*)my_img)[(ci < 3 ? ci : 2) * 256 + yc * 8 + (rem & 7)];
-      }
+    } else {      // last block: the next batch's image quarter and label, stored at the kernel's end (the stem backward
+                  // itself consumes no global load: pool codes and input copies wait in LDS since the forward)
       if (t < 48) nxt = ((const uint4*)(cx.data + (size_t)next_id * 3072 + 768 * s))[t];
       if (t == 48) nxt_lab = cx.labels[next_id];
     }
@@ -1747,7 +1811,7 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     // dgrad: g_i = g_{i+1} + conv(dy, W^T flipped)
     if (i > 0) st4n = stat[(i - 1) * 32 + ch];
     {
-      const f32x4 acc = conv_row<P>(XR, WT, bw, w, hh, lane);
+      const f32x4 acc = conv_row<P>(XR, WTD, bw, w, hh, lane);
 #pragma unroll
       for (int i2 = 0; i2 < 4; ++i2) g[i2] += acc[i2];
     }
@@ -1770,8 +1834,20 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     asm volatile("v_mov_b32 %0, %1" : "=v"(tf) : "v"(tf));
     const int t = tf, wv = tf >> 6, lane = tf & 63, c = lane & 15, q = lane >> 4;
     const int w = wv & (RS - 1), ch = 16 * (wv / RS) + c;
+    // trunk wgrad slab (accumulated over the 10 applications): tile tt = 2 nt + mt, the layout the reduction reads.
+    // Issued here, ahead of the stem backward: that phase consumes no global load any more (pool codes and input
+    // copies wait in LDS since the forward), so it has no vmcnt wait these in-order write-through stores could hold
+    // up, and their drain overlaps its LDS and MFMA work instead of standing alone at the kernel's end.
+#pragma unroll
+    for (int j = 0; j < NNT; ++j) {
+      const int nt = wv + NW * j;
+      if (nt < 18) {
+        st4_wt(pa.tslab + (size_t)L * WSLAB_N + (((2 * nt) * 64 + lane) << 2), wacc[j][0]);
+        st4_wt(pa.tslab + (size_t)L * WSLAB_N + (((2 * nt + 1) * 64 + lane) << 2), wacc[j][1]);
+      }
+    }
+    const unsigned codew = codes[t];
     unsigned short* dsT = (unsigned short*)(U + PL::U_DST);
-    unsigned short* xs = (unsigned short*)(U + PL::U_XS);
     float* sred = (float*)(U + PL::U_SRED);
     // d(conv1 output) of this row's two conv rows, channel ch: every 2x2 window written whole (value at the
     // argmax if the ReLU was active, zeros elsewhere)
@@ -1790,36 +1866,6 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
         *(unsigned*)(dsT + PL::DST_PL / 2 + so + 32) = (pos == 2 ? vl : 0u) | ((pos == 3 ? vl : 0u) << 16);
       }
       db += val;
-    }
-    // three column-shifted copies of the normalised input rows 8s-1 .. 8s+8 (copy kw holds x[col + kw - 1])
-    if (t < 240) {
-      const int ci = t / 80, rem = t % 80, xr_ = rem >> 3, x0 = 4 * (rem & 7), yimg = 8 * s - 1 + xr_;
-      const bool valid = yimg >= 0 && yimg < 32;
-      unsigned hb[4], lb[4];
-#pragma unroll
-      for (int b2 = 0; b2 < 4; ++b2) {
-        const float v = valid ? norm_px((imgw >> (8 * b2)) & 255u, ci) : 0.f;
-        const unsigned short hi = bfbits(v);
-        hb[b2] = hi;
-        lb[b2] = P == 1 ? bf_lo(v, hi) : 0u;
-      }
-#pragma unroll
-      for (int p = 0; p <= P; ++p) {
-        const unsigned* bb = p ? lb : hb;
-        unsigned short* base = xs + p * (PL::XS_PL / 2);
-        unsigned short* p1 = base + ((3 + ci) * PL::XSR + xr_) * PL::XS_S + x0;  // kw = 1
-        *(uint2*)p1 = uint2{bb[0] | (bb[1] << 16), bb[2] | (bb[3] << 16)};
-        unsigned short* p0 = base + ((0 + ci) * PL::XSR + xr_) * PL::XS_S + x0;  // kw = 0: col c holds x[c - 1]
-        p0[1] = (unsigned short)bb[0];
-        *(unsigned*)(p0 + 2) = bb[1] | (bb[2] << 16);
-        if (x0 + 4 < 32) p0[4] = (unsigned short)bb[3];
-        if (x0 == 0) p0[0] = 0;
-        unsigned short* p2 = base + ((6 + ci) * PL::XSR + xr_) * PL::XS_S + x0;  // kw = 2: col c holds x[c + 1]
-        if (x0 > 0) p2[-1] = (unsigned short)bb[0];
-        *(unsigned*)p2 = bb[1] | (bb[2] << 16);
-        p2[2] = (unsigned short)bb[3];
-        if (x0 == 28) p2[3] = 0;
-      }
     }
     // conv1 bias gradient partial of this workgroup (also the barrier before the MFMAs)
     const float dbv = wg_csum<true>(db, 0.f, cred);
@@ -1855,22 +1901,12 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     }
   }
   DCA_STAMP(cx, 5, L, 4);
-  // the next batch's image n (this slice's quarter) and label, staged into the other parity
+  // the next batch's image n (this slice's quarter) and label, staged into the other parity.  Last: the wait for the
+  // load above is the kernel's only vmcnt wait after the slab stores, and here everything has to drain anyway.
+  // (Loaded after forward block 1's exchange and stored after block 2's instead: 0.2 us per step slower, see
+  // docs/ARCHITECTURE.md.)
   if (t < 48) st4_wt((uint4*)(pa.simg + (size_t)((par ^ 1) * 64 + n) * 3072 + 768 * s) + t, __builtin_bit_cast(f32x4, nxt));
   if (t == 48 && s == 0) pa.slab[(par ^ 1) * 64 + n] = nxt_lab;
-  // trunk wgrad slab (accumulated over the 10 applications): tile tt = 2 nt + mt, the layout the reduction reads.
-  // (Issued here, last: stored right after application 0's wgrad instead, the write-through stores held up the stem
-  // backward's own waits -- vmcnt retires in order -- and the step was no faster.)
-  int wvf = wv;  // opaque copy: the slab offsets are re-derived here, not held live (spilled) since the forward
-  asm volatile("v_mov_b32 %0, %1" : "=v"(wvf) : "v"(wvf));
-#pragma unroll
-  for (int j = 0; j < NNT; ++j) {
-    const int nt = wvf + NW * j;
-    if (nt < 18) {
-      st4_wt(pa.tslab + (size_t)L * WSLAB_N + (((2 * nt) * 64 + lane) << 2), wacc[j][0]);
-      st4_wt(pa.tslab + (size_t)L * WSLAB_N + (((2 * nt + 1) * 64 + lane) << 2), wacc[j][1]);
-    }
-  }
   DCA_STAMP(cx, 5, L, 7);
 }
 

@@ -1,6 +1,6 @@
 """ResNet-50 stem conv (space-to-depth 4x4 over 16 channels, batch 256 at 224) bf16 + BN column statistics, event-timed.
 
-    python bench/stem_conv_bench.py          (DCA_OPS_CONV_ROWS=0: the k_direct_conv<16, 4, 4> form)
+    python bench/stem_conv_bench.py
 """
 import json
 import os

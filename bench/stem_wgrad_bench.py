@@ -1,6 +1,6 @@
 """ResNet-50 stem weight gradient (s2d 4x4 over 16 channels, batch 256 at 224), incl. the split-K reduce, event-timed.
 
-    python bench/stem_wgrad_bench.py          (DCA_OPS_WGRAD_ROWS=0: the k_wgrad form)
+    python bench/stem_wgrad_bench.py
 """
 import json
 import os

@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _lock = threading.Lock()
 _lib = None
 
@@ -35,6 +35,13 @@ class GemmArgs(ctypes.Structure):
         ("orow_W", c_int), ("orow_Ho", c_int), ("orow_Wo", c_int),
         ("beta_src", c_void_p), ("beta_mask", c_void_p),
     ]
+
+
+class GemmRoute(ctypes.Structure):
+    """Mirror of csrc/ops_gemm_route.hip::GemmRoute: the kernel and launch dca_ops_gemm chooses for a GemmArgs."""
+    _fields_ = [("kernel", c_int), ("name", ctypes.c_char_p), ("grid_x", c_int), ("grid_y", c_int), ("block", c_int),
+                ("lds", c_int), ("splits", c_int), ("k_per_split", c_int), ("single", c_int), ("stages", c_int),
+                ("masked_copy", c_int), ("reduce", c_int)]
 
 
 class ConvGeom(ctypes.Structure):
@@ -61,6 +68,8 @@ def _declare(lib):
     lib.dca_ops_abi_version.restype = c_int
     P = ctypes.POINTER
     lib.dca_ops_gemm.argtypes = [P(GemmArgs), c_void_p]
+    lib.dca_ops_gemm_route.argtypes = [P(GemmArgs), c_int, c_int, P(GemmRoute)]
+    lib.dca_ops_gemm_last_route.argtypes = [P(GemmRoute)]
     lib.dca_ops_im2col.argtypes = [c_void_p, c_void_p, P(ConvGeom), c_void_p]
     lib.dca_ops_col2im.argtypes = [c_void_p, c_void_p, P(ConvGeom), c_int, c_void_p]
     lib.dca_ops_bn_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -80,7 +89,8 @@ def _declare(lib):
                                               c_void_p, c_float, c_float, c_void_p, c_void_p, P(PoolGeom), c_void_p,
                                               c_void_p]
     lib.dca_ops_bn_pool_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(PoolGeom), c_void_p, c_void_p]
+                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(PoolGeom), c_void_p,
+                                        c_void_p]
     lib.dca_ops_avgpool_fwd.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.dca_ops_avgpool_bwd.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.dca_ops_cross_entropy.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p,
@@ -133,6 +143,13 @@ def lib():
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise RuntimeError(f"{what} failed: {lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def last_gemm_kernel() -> str:
+    """The kernel this thread's last gemm launched, spelled as in the source (e.g. ``k_conv3x3_rows<2, 128>``)."""
+    r = GemmRoute()
+    check(lib().dca_ops_gemm_last_route(ctypes.byref(r)), "gemm_last_route")
+    return r.name.decode()
 
 
 def ptr(t):

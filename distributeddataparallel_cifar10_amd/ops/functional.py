@@ -21,9 +21,6 @@ from . import _native as N
 
 _BWD_TRACE = None  # diagnostics: a list to record the order of the fused conv-BN backward calls
 WGRAD_NARROW_HALF = True  # _wgrad_splits' halved target for the narrow forms (False: the round-6 rule, for A/Bs)
-# the row-ring weight gradient of the 64-channel 3x3 convs (csrc/ops_wgrad.hip k_wgrad3x3_rows) is on unless either
-# of its native knobs turns it off; it sets that form's split count (_wgrad_splits)
-WGRAD_ROWS = os.environ.get("DCA_OPS_WGRAD_ROWS", "1") != "0" and os.environ.get("DCA_OPS_CONV_ROWS", "1") != "0"
 
 
 def _dev_check(*ts):
@@ -157,11 +154,11 @@ def _wgrad_splits(M: int, Nn: int, K: int, implicit: bool = False, row_w: int = 
     one on rows <= 32 pixels two workgroups per slab, one per CU: 128 splits; the s2d stem's (k_wgrad_s2d_rows)
     three per CU: 768 (150 -> 143 us over 512; 128 / 96 / 64 and 512 / 384 / 256 for the 3x3 forms measured slower:
     profiles/wgrad_rows_splits_r9q.log).  row_w: input row width of a KH > 1 implicit conv, else 0."""
-    if implicit and M == 64 and Nn == 576 and 0 < row_w <= 64 and WGRAD_ROWS:
+    if implicit and M == 64 and Nn == 576 and 0 < row_w <= 64:
         return max(1, min(512, K // 256))
-    if implicit and M == 128 and Nn == 1152 and 0 < row_w <= 32 and WGRAD_ROWS:  # layer 2: 2 workgroups per split
+    if implicit and M == 128 and Nn == 1152 and 0 < row_w <= 32:  # layer 2: 2 workgroups per split
         return max(1, min(128, K // 256))
-    if implicit and M == 64 and Nn == 256 and 0 < row_w <= 128 and WGRAD_ROWS:  # s2d stem: 3 workgroups per CU
+    if implicit and M == 64 and Nn == 256 and 0 < row_w <= 128:  # s2d stem: 3 workgroups per CU
         return max(1, min(768, K // 256))
     tiles = math.ceil(M / 128) * math.ceil(Nn / 128)
     narrow = (min(M, Nn) <= 64) if not implicit else (min(M, Nn) == 128)
@@ -1033,9 +1030,9 @@ def _bn_pool_backward(dp, arg, y, gamma, beta, stats, pg, dgamma_out=None, dbeta
     dbeta = dbeta_out if direct else torch.empty_like(dgamma)
     dy = torch.empty_like(y)
     N.check(N.lib().dca_ops_bn_pool_bwd(N.ptr(dp), N.ptr(arg), N.ptr(y), N.ptr(stats), N.ptr(gamma), N.ptr(beta),
-                                        N.ptr(part), N.ptr(sums), N.ptr(dgamma), N.ptr(dbeta), N.ptr(dy), int(direct),
-                                        pg, N.ptr(_ticket(y.device, (C + 63) // 64)), N.stream(y.device)),
-            "bn_pool_bwd")
+                                        N.ptr(part), part.shape[0], N.ptr(sums), N.ptr(dgamma), N.ptr(dbeta), N.ptr(dy),
+                                        int(direct), pg, N.ptr(_ticket(y.device, (C + 63) // 64)),
+                                        N.stream(y.device)), "bn_pool_bwd")
     return dy, (None if direct else dgamma), (None if direct else dbeta)
 
 

@@ -115,12 +115,102 @@ def test_ops_reject_cpu_tensors():
         ops.gemm(torch.zeros(4, 8, dtype=torch.bfloat16), torch.zeros(4, 8, dtype=torch.bfloat16))
 
 
-def test_wgrad_split_rules_for_the_row_kernels(monkeypatch):
+_GEMM_PTRS = ("A", "B", "C", "bias", "ws", "alpha_dev", "col_stats", "stats_shift", "amax_a", "amax_b", "beta_src",
+              "beta_mask")
+_ROUTE_FIELDS = ("grid_x", "grid_y", "block", "lds", "splits", "k_per_split", "single", "stages", "masked_copy",
+                 "reduce")
+
+
+def _ops_lib():
+    from distributeddataparallel_cifar10_amd.ops import _native
+    lib = _native._declare(ctypes.CDLL(nbuild.build(variant="ops"), mode=ctypes.RTLD_GLOBAL))
+    return lib, _native
+
+
+def _gemm_args(_native, fields):
+    """A GemmArgs from a fixture's fields; a pointer is null (None) or a distinct address with the recorded low four
+    bits (the rule reads only null-ness, alignment and beta_src != C; nothing is dereferenced)."""
+    a = _native.GemmArgs()
+    for k, v in fields.items():
+        if k in _GEMM_PTRS:
+            v = None if v is None else ((_GEMM_PTRS.index(k) + 1) << 20) | v
+        setattr(a, k, v)
+    return a
+
+
+def _route(lib, _native, fields, ncu=256, stream_mode=2):
+    r = _native.GemmRoute()
+    rc = lib.dca_ops_gemm_route(ctypes.byref(_gemm_args(_native, fields)), ncu, stream_mode, ctypes.byref(r))
+    return rc, r
+
+
+def test_gemm_routes_match_golden():
+    """dca_ops_gemm_route (csrc/ops_gemm_route.hip, no device needed) against tests/golden/gemm_routes.json: the
+    kernel, grid, block, LDS bytes, rewritten GemmArgs fields, masked copy and reduce pass of every case -- every
+    distinct GEMM of a ResNet-50 training step at batch 256 / 224^2 and batch 3 / 96^2, both sides of every threshold
+    the rule names, DCA_OPS_STREAM 0 / 1 on the shapes of tests/_stream_check.py, and other CU counts.  The expected
+    values were recorded from the launches of the dispatcher this rule replaced (its hipLaunchKernelGGL redirected
+    to a printer on the CPU), never from the rule under test.  A route never asks for more splits than requested:
+    the caller sized the workspace for the requested count."""
+    import json
+    lib, _native = _ops_lib()
+    cases = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "gemm_routes.json")))
+    assert len(cases) > 600
+    ids, bad = {}, []
+    for c in cases:
+        rc, r = _route(lib, _native, c["args"], c["ncu"], c["stream_mode"])
+        if rc != 0:
+            bad.append((c["name"], lib.dca_ops_last_error().decode()))
+            continue
+        got = dict({f: getattr(r, f) for f in _ROUTE_FIELDS}, name=r.name.decode())
+        if got != c["route"] or got["splits"] > max(1, c["args"].get("splits", 0)):
+            bad.append((c["name"], got, c["route"]))
+        assert ids.setdefault(got["name"], r.kernel) == r.kernel  # one id per kernel name
+    assert not bad, bad[:10]
+    assert len(ids) == 49 and sorted(ids.values()) == list(range(49))  # every instantiation keeps a route
+
+
+def test_gemm_route_rejects_bad_shapes():
+    """One shape per class of check that integers alone reach: -1 and a message, with no device and no launch."""
+    lib, _native = _ops_lib()
+    ok = dict(A=0, B=0, C=0, M=256, N=128, K=256, lda=256, ldb=256, ldc=128, alpha=1.0, out_bf16=1, splits=1)
+    conv = dict(ok, conv=1, M=2 * 8 * 8, K=9 * 64, ldb=9 * 64, lda=0, cN=2, cH=8, cW=8, cC=64, cKH=3, cKW=3, cS=1,
+                cP=1, cHo=8, cWo=8)
+    assert _route(lib, _native, ok)[0] == 0 and _route(lib, _native, conv)[0] == 0
+    for what, fields in (("empty problem", dict(ok, M=0)),
+                         ("lda < K", dict(ok, lda=255)),
+                         ("inconsistent conv geometry", dict(conv, cHo=9, M=2 * 9 * 8)),
+                         ("split-K needs a workspace", dict(ok, splits=2)),
+                         ("column stats", dict(ok, splits=2, ws=0, col_stats=0, stats_shift=0)),
+                         ("masked accumulation source", dict(ok, beta=0.0, beta_mask=0, beta_src=0)),
+                         ("fp8", dict(ok, fp8=1, K=250, lda=250, ldb=250)),
+                         ("bad conv mode", dict(ok, conv=3)),
+                         ("weight-layout remap", dict(ok, wperm_T=9, wperm_C=3, wperm_Cpad=8)),
+                         ("output row remap", dict(ok, orow_S=2, orow_Ho=3, orow_Wo=5, orow_H=6, orow_W=10))):
+        rc, _ = _route(lib, _native, fields)
+        assert rc == -1 and what in lib.dca_ops_last_error().decode(), (what, rc, lib.dca_ops_last_error())
+    # a masked source equal to C: the same address for both
+    a = _gemm_args(_native, dict(ok, beta=1.0, beta_mask=0, beta_src=0))
+    a.beta_src = a.C
+    assert lib.dca_ops_gemm_route(ctypes.byref(a), 256, 2, ctypes.byref(_native.GemmRoute())) == -1
+    assert b"masked accumulation source" in lib.dca_ops_last_error()
+
+
+def test_bn_pool_bwd_rejects_a_short_partial_buffer():
+    """dca_ops_bn_pool_bwd checks the caller's partial-sum row count against ceil(N Ho Wo / 64) before any launch."""
+    lib, _native = _ops_lib()
+    pg = _native.PoolGeom(N=2, H=16, W=16, C=64, K=3, S=2, P=1, Ho=8, Wo=8)  # 128 pooled pixels: 2 rows
+    rc = lib.dca_ops_bn_pool_bwd(None, None, None, None, None, None, None, 1, None, None, None, None, 0,
+                                 ctypes.byref(pg), None, None)
+    assert rc == -1 and b"bn_pool bwd" in lib.dca_ops_last_error()
+
+
+def test_wgrad_split_rules_for_the_row_kernels():
     """ops/functional.py _wgrad_splits: the row-ring weight gradients (csrc/ops_wgrad.hip) get one split slab per
     workgroup -- 512 for the 64-channel 3x3 on rows <= 64 pixels, 128 for the 128-channel one on rows <= 32, 768 for
-    the s2d stem on rows <= 128 -- and every other shape, or the knob off, keeps the k_wgrad rule."""
+    the s2d stem on rows <= 128 -- and every other shape keeps the k_wgrad rule; with Python's split count the native
+    rule sends the three row shapes to the row kernels."""
     from distributeddataparallel_cifar10_amd.ops import functional as F
-    monkeypatch.setattr(F, "WGRAD_ROWS", True)
     k1, k2 = 256 * 56 * 56, 256 * 28 * 28
     assert F._wgrad_splits(64, 576, k1, True, row_w=56) == 512
     assert F._wgrad_splits(64, 576, 1000, True, row_w=10) == 3  # K // 256
@@ -131,8 +221,17 @@ def test_wgrad_split_rules_for_the_row_kernels(monkeypatch):
     assert (old1, old2) == (205, 57)
     assert F._wgrad_splits(64, 576, k1, True, row_w=70) == old1
     assert F._wgrad_splits(128, 1152, k2, True, row_w=40) == old2
-    monkeypatch.setattr(F, "WGRAD_ROWS", False)
-    assert F._wgrad_splits(64, 576, k1, True, row_w=56) == old1
+    lib, _native = _ops_lib()
+    for (c, k, pad, hw, co), kernel in (((64, 3, 1, 56, 64), "k_wgrad3x3_rows<2>"),
+                                        ((128, 3, 1, 28, 128), "k_wgrad3x3_rows<1, 128>"),
+                                        ((16, 4, 0, 115, 64), "k_wgrad_s2d_rows<4>")):
+        ho = hw + 2 * pad - k + 1
+        M, Nn, K = co, k * k * c, 256 * ho * ho
+        sp = F._wgrad_splits(M, Nn, K, True, row_w=hw)
+        rc, r = _route(lib, _native, dict(A=0, B=0, C=0, ws=0, M=M, N=Nn, K=K, lda=M, ldc=Nn, alpha=1.0, ta=1,
+                                          splits=sp, conv=2, cN=256, cH=hw, cW=hw, cC=c, cKH=k, cKW=k, cS=1, cP=pad,
+                                          cHo=ho, cWo=ho))
+        assert rc == 0 and r.name.decode() == kernel and 1 < r.splits <= sp and r.reduce == 1, (kernel, r.name, r.splits)
 
 
 def test_row_kernel_lds_maps_are_conflict_free():

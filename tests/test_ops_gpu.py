@@ -38,11 +38,12 @@ def test_gemm_bf16(gpu, M, N, K, ta, tb):
 
 def test_gemm_pingpong_matches_torch(gpu):
     """The ping-pong 256 x 256 GEMMs on shapes the production rule routes to them (N % 256 == 0, >= 160 output
-    tiles): k_gemm_pp4 (K % 64 == 0, K >= 512) and k_gemm_pp (K = 1040: K % 64 != 0, K >= 1024); plain NT with M / K
+    tiles): k_gemm_pp4 (K % 64 == 0, K >= 512) and k_gemm_pp (K = 1040: K % 64 != 0, K >= 512); plain NT with M / K
     tails, bf16 output + bias + ReLU, the fused BN column statistics, and an implicit 3x3 convolution with C % 64 == 0
-    -- against torch fp32."""
+    -- against torch fp32.  Every call asserts the kernel it ran."""
     from distributeddataparallel_cifar10_amd import ops
     from distributeddataparallel_cifar10_amd.ops import functional as F
+    from distributeddataparallel_cifar10_amd.ops._native import last_gemm_kernel
     g = torch.Generator(device=gpu).manual_seed(0)
     bf = torch.bfloat16
     for M, N, K in [(4096, 2560, 1024), (4000, 2560, 1040), (4000, 2560, 576)]:
@@ -50,11 +51,15 @@ def test_gemm_pingpong_matches_torch(gpu):
         b = torch.randn(N, K, device=gpu, generator=g).to(bf)
         bias = torch.randn(N, device=gpu, generator=g)
         ref = a.float() @ b.float().t()
+        kernel = "k_gemm_pp<256>" if K == 1040 else "k_gemm_pp4<false>"
         assert _rel(ops.gemm(a, b, out_dtype=torch.float32), ref) < 2e-3
+        assert last_gemm_kernel() == kernel
         assert _rel(ops.gemm(a, b, bias=bias, relu=True, out_dtype=bf).float(), torch.relu(ref + bias)) < 1e-2
+        assert last_gemm_kernel() == kernel
         shift = torch.randn(N, device=gpu, generator=g) * 0.1
         parts = torch.empty((M + 127) // 128, N, 2, device=gpu)
         y = ops.gemm(a, b, out_dtype=bf, col_stats=parts, stats_shift=shift)
+        assert last_gemm_kernel() == kernel
         d = y.float() - shift
         assert _rel(parts[..., 0].sum(0), d.sum(0)) < 1e-2 and _rel(parts[..., 1].sum(0), (d * d).sum(0)) < 1e-2
     x = torch.randn(64, 26, 26, 128, device=gpu, generator=g).to(bf)  # 43264 x 256 x 1152: 169 tiles
@@ -63,6 +68,7 @@ def test_gemm_pingpong_matches_torch(gpu):
     wm = F._weight_matrix(w, geo.K)
     Mc = geo.N * geo.Ho * geo.Wo
     y = ops.gemm(x, wm, conv=1, geom=geo, mnk=(Mc, 256, geo.K), out_dtype=torch.float32)
+    assert last_gemm_kernel() == "k_gemm_pp4<true>"
     ref = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w.to(bf).float(), padding=1)
     assert _rel(y.view(64, 26, 26, 256).permute(0, 3, 1, 2), ref) < 2e-3
 
@@ -74,6 +80,7 @@ def test_gemm_256_exact_integers(gpu):
     exactly)."""
     from distributeddataparallel_cifar10_amd import ops
     from distributeddataparallel_cifar10_amd.ops import functional as F
+    from distributeddataparallel_cifar10_amd.ops._native import last_gemm_kernel
     g = torch.Generator(device=gpu).manual_seed(5)
     bf = torch.bfloat16
     for M, N, K, lda in [(4096, 2560, 1024, 1024), (4000, 2560, 2048, 2056), (4096, 4096, 4096, 4096)]:
@@ -81,12 +88,14 @@ def test_gemm_256_exact_integers(gpu):
         b = torch.randint(-3, 4, (N, K), device=gpu, generator=g).to(bf)
         ref = (a.double() @ b.double().t()).float()
         out = ops.gemm(a, b, out_dtype=torch.float32)
+        assert last_gemm_kernel() == "k_gemm_pp4<false>"
         assert torch.equal(out, ref), (M, N, K, (out - ref).abs().max().item())
     x = torch.randint(-2, 3, (64, 26, 26, 128), device=gpu, generator=g).to(bf)  # 43264 x 256 x 1152: 169 tiles
     w = torch.randint(-2, 3, (256, 128, 3, 3), device=gpu, generator=g).float()
     geo = F._geom(x, w, 1, 1)
     wm = F._weight_matrix(w, geo.K)
     y = ops.gemm(x, wm, conv=1, geom=geo, mnk=(geo.N * geo.Ho * geo.Wo, 256, geo.K), out_dtype=torch.float32)
+    assert last_gemm_kernel() == "k_gemm_pp4<true>"
     ref = torch.nn.functional.conv2d(x.double().permute(0, 3, 1, 2), w.double(), padding=1).float()
     assert torch.equal(y.view(64, 26, 26, 256).permute(0, 3, 1, 2), ref)
 
@@ -723,9 +732,10 @@ def test_wgrad_pingpong_implicit_conv(gpu, n, h, c, co, k, s, p):
 def test_wgrad3x3_rows(gpu, n, h, w, c):
     """The 64- / 128-channel 3x3 / pad 1 weight gradients as the model calls them (implicit split count): W <= 64 /
     32 run the row-ring k_wgrad3x3_rows<ceil(W / 32), C> (one and two 32-pixel chunks, pixels past W, padding rows,
-    one split slab per workgroup -- per output-channel half for 128), W = 70 / 40 the k_wgrad / ping-pong fallbacks;
-    against torch fp32 in torch's [Cout, Cin, 3, 3] layout."""
+    one split slab per workgroup -- per output-channel half for 128), W = 70 / 40 the k_wgrad fallbacks (64 x 128 /
+    128 x 128 tiles); against torch fp32 in torch's [Cout, Cin, 3, 3] layout."""
     from distributeddataparallel_cifar10_amd.ops import functional as F
+    from distributeddataparallel_cifar10_amd.ops._native import last_gemm_kernel
     g = torch.Generator(device=gpu).manual_seed(n * h + w + c)
     x = _bf(torch.randn(n, h, w, c, device=gpu, generator=g))
     wt = torch.empty(c, c, 3, 3, device=gpu)
@@ -737,6 +747,10 @@ def test_wgrad3x3_rows(gpu, n, h, w, c):
     out = torch.full_like(wt, float("nan"))
     F.gemm(dy, x, ta=True, conv=2, geom=geo, mnk=(c, geo.K, M), splits=F._wgrad_splits(c, geo.K, M, True, row_w=w),
            out=out, wperm=(c, c, 9))
+    if c == 64:
+        assert last_gemm_kernel() == (f"k_wgrad3x3_rows<{(w + 31) // 32}>" if w <= 64 else "k_wgrad<64, 128, 1>")
+    else:
+        assert last_gemm_kernel() == ("k_wgrad3x3_rows<1, 128>" if w <= 32 else "k_wgrad<128, 128, 2>")
     assert _rel(out, ref) < 1e-5, _rel(out, ref)
 
 
@@ -968,9 +982,11 @@ def test_direct_conv_3x3_64(gpu, n, h, w, c):
     fp32 on the same bf16-rounded operands: padding on every border, M tails, the statistics rows (all of them
     written: the buffer starts as NaN).  64 channels: W <= 64 runs the row-ring kernel k_conv3x3_rows<ceil(W / 16)>
     (one to four fragments), W = 70 the per-pixel k_direct_conv<64, 3, 3>; 128 channels: W <= 32 runs
-    k_conv3x3_rows<ceil(W / 16), 128> (ResNet-50's layer 2 at 28 x 28), W = 40 the stream GEMM."""
+    k_conv3x3_rows<ceil(W / 16), 128> (ResNet-50's layer 2 at 28 x 28), W = 40 k_gemm_glds<false, 128, 8> (M = 240
+    is far below the stream kernel's 16384 rows)."""
     from distributeddataparallel_cifar10_amd import ops
     from distributeddataparallel_cifar10_amd.ops import functional as F
+    from distributeddataparallel_cifar10_amd.ops._native import last_gemm_kernel
     g = torch.Generator(device=gpu).manual_seed(n * h + w + c)
     x = torch.randn(n, h, w, c, device=gpu, generator=g).to(torch.bfloat16)
     wt = torch.randn(c, c, 3, 3, device=gpu, generator=g) * (0.05 if c == 64 else 0.035)
@@ -981,6 +997,11 @@ def test_direct_conv_3x3_64(gpu, n, h, w, c):
     parts = torch.full(((M + 127) // 128, c, 2), float("nan"), device=gpu)
     y = ops.gemm(x, wm, conv=1, geom=geo, mnk=(M, c, geo.K), out_dtype=torch.bfloat16, col_stats=parts,
                  stats_shift=shift)
+    if c == 64:
+        assert last_gemm_kernel() == (f"k_conv3x3_rows<{(w + 15) // 16}>" if w <= 64 else "k_direct_conv<64, 3, 3>")
+    else:
+        assert last_gemm_kernel() == (f"k_conv3x3_rows<{(w + 15) // 16}, 128>" if w <= 32
+                                      else "k_gemm_glds<false, 128, 8>")
     ref = TF.conv2d(x.float().permute(0, 3, 1, 2), wt.to(torch.bfloat16).float(), padding=1)
     ref = ref.permute(0, 2, 3, 1).reshape(M, c)
     assert _rel(y, ref) < 5e-3

@@ -128,6 +128,8 @@ def test_stem_conv_kernel_bf16_stats(gpu, n, h, w):
     parts = torch.full(((M + 127) // 128, 64, 2), float("nan"), device=gpu)
     y = F.gemm(xs, e["fwd"], conv=1, geom=g, mnk=(M, 64, g.K), out_dtype=torch.bfloat16, col_stats=parts,
                stats_shift=shift)
+    from distributeddataparallel_cifar10_amd.ops._native import last_gemm_kernel
+    assert last_gemm_kernel() == (f"k_conv_s2d_rows<{(g.Wo + 15) // 16}>" if g.W <= 128 else "k_direct_conv<16, 4, 4>")
     xr = x.to(torch.bfloat16).float()
     wr = conv.weight.detach().to(torch.bfloat16).float()
     ref = TF.conv2d(xr, wr, stride=2, padding=3).permute(0, 2, 3, 1).reshape(M, 64)
@@ -158,6 +160,8 @@ def test_stem_wgrad_rows(gpu, n, h, w):
     d4 = torch.full((64, 16, 4, 4), float("nan"), device=gpu)
     F.gemm(dy, xs, ta=True, conv=2, geom=g, mnk=(64, g.K, M), splits=F._wgrad_splits(64, g.K, M, True, row_w=g.W),
            out=d4, wperm=(16, 16, 16))
+    from distributeddataparallel_cifar10_amd.ops._native import last_gemm_kernel
+    assert last_gemm_kernel() == (f"k_wgrad_s2d_rows<{(g.Wo + 31) // 32}>" if g.W <= 128 else "k_wgrad<64, 128, 1>")
     dw = d4.view(64, -1).index_select(1, e["s2d"]["back_idx"]).view(64, 3, 7, 7)
     xr = x.to(torch.bfloat16).float()
     gref = torch.nn.grad.conv2d_weight(xr, conv.weight.shape, dy.float().view(g.N, g.Ho, g.Wo, 64).permute(0, 3, 1, 2),

@@ -42,6 +42,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));  // 4 bf16 bit patterns (16x16x16 MFMA operand)
 
+__device__ __forceinline__ unsigned short bfbits(float f) {
+  return __builtin_bit_cast(unsigned short, (__bf16)f);
+}
+__device__ __forceinline__ f32x4 z4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+
 // Everything a kernel needs, passed by value (kernarg segment).
 struct Ctx {
   int B;          // images in this step (ragged last batch supported)

@@ -20,6 +20,7 @@
 #include "netresdeep_kernels.hip"
 #include "xgmi_allreduce.hip"
 #include "netresdeep_pks.hip"
+#include "netresdeep_eval.hip"
 
 namespace {
 
@@ -482,7 +483,7 @@ extern "C" {
 
 const char* dca_last_error() { return g_err.c_str(); }
 
-int dca_abi_version() { return 7; }  // bump with every DcaInit / signature change
+int dca_abi_version() { return 8; }  // bump with every DcaInit / signature change
 
 int dca_nccl_unique_id(char* out128) {
   ncclUniqueId id;
@@ -1191,5 +1192,80 @@ int dca_engine_kind(void* h) {
   return e->persistent ? 2 : 0;
 }
 
+// Must match runtime/evaluate.py::_DcaEvalArgs field by field.
+struct DcaEvalArgs {
+  const float* conv1_w;  // [32][3][3][3]   fp32 master tensors (not the engine's derived copies), device pointers
+  const float* conv1_b;  // [32]
+  const float* conv_w;   // [32][32][3][3]  the one shared trunk conv
+  const float* bn_w;     // [32]
+  const float* bn_b;     // [32]
+  const float* bn_rm;    // [32] running_mean
+  const float* bn_rv;    // [32] running_var
+  const float* fc1_w;    // [32][2048]      (16-byte aligned)
+  const float* fc1_b;    // [32]
+  const float* fc2_w;    // [10][32]
+  const float* fc2_b;    // [10]
+  float bn_eps;
+  const uint8_t* data;   // [n_data][3][32][32]
+  const int* labels;     // [n_data]
+  int n_data;
+  const int* indices;    // [n] device int32 (clamped into [0, n_data) by the kernel)
+  int n;
+  int bf16;              // 1: bf16 conv operands + bf16 fc1 weight; 0: 3xbf16 conv, fp32 conv1 / fc1
+  int max_workgroups;    // 0: every workgroup slot of the device
+  float* logits;         // [n][10] or null
+  int* pred;             // [n]
+  float* loss;           // [n]
+};
+
+// Eval-mode forward of `n` gathered images (netresdeep_eval.hip), enqueued on `stream`.  Everything is validated on
+// the host before any device call: a bad argument returns -1 with a message and launches nothing.
+int dca_eval_netresdeep(const DcaEvalArgs* a, void* stream) {
+  if (!a) {
+    g_err = "dca_eval_netresdeep: null argument block";
+    return -1;
+  }
+  const void* ptrs[] = {a->conv1_w, a->conv1_b, a->conv_w, a->bn_w,   a->bn_b, a->bn_rm,   a->bn_rv, a->fc1_w,
+                        a->fc1_b,   a->fc2_w,   a->fc2_b,  a->data,   a->labels, a->indices, a->pred, a->loss};
+  const char* names[] = {"conv1_w", "conv1_b", "conv_w", "bn_w", "bn_b",   "bn_rm",   "bn_rv", "fc1_w",
+                         "fc1_b",   "fc2_w",   "fc2_b",  "data", "labels", "indices", "pred",  "loss"};
+  for (int i = 0; i < 16; ++i) {
+    if (!ptrs[i]) {
+      g_err = std::string("dca_eval_netresdeep: null pointer: ") + names[i];
+      return -1;
+    }
+    // fc1_w is read in 16-byte pieces; every other tensor in 4-byte words (the image bytes too)
+    const uintptr_t align = i == 7 ? 16 : 4;
+    if ((uintptr_t)ptrs[i] % align) {
+      g_err = std::string("dca_eval_netresdeep: misaligned pointer: ") + names[i];
+      return -1;
+    }
+  }
+  if (a->logits && (uintptr_t)a->logits % 4) {
+    g_err = "dca_eval_netresdeep: misaligned pointer: logits";
+    return -1;
+  }
+  if (a->n <= 0 || a->n_data <= 0) {
+    g_err = "dca_eval_netresdeep: n and n_data must be positive";
+    return -1;
+  }
+  if (a->max_workgroups < 0 || !(a->bn_eps >= 0.f)) {
+    g_err = "dca_eval_netresdeep: max_workgroups and bn_eps must not be negative";
+    return -1;
+  }
+  const int P = a->bf16 ? 0 : 1;
+  int dev = 0;
+  HIPCK(hipGetDevice(&dev));
+  int grid = a->max_workgroups > 0 ? a->max_workgroups : dca::nrd_eval::default_workgroups(P, dev);
+  if (grid > a->n) grid = a->n;
+  dca::nrd_eval::Args ka{a->conv1_w, a->conv1_b, a->conv_w, a->bn_w, a->bn_b, a->bn_rm, a->bn_rv, a->fc1_w, a->fc1_b,
+                         a->fc2_w,   a->fc2_b,   a->bn_eps, a->data, a->labels, a->n_data, a->indices, a->n,
+                         a->logits,  a->pred,    a->loss};
+  hipStream_t st = (hipStream_t)stream;
+  if (P == 0) hipLaunchKernelGGL(dca::nrd_eval::k_nrd_eval<0>, dim3(grid), dim3(dca::nrd_eval::NTH), 0, st, ka);
+  else hipLaunchKernelGGL(dca::nrd_eval::k_nrd_eval<1>, dim3(grid), dim3(dca::nrd_eval::NTH), 0, st, ka);
+  HIPCK(hipGetLastError());
+  return 0;
+}
 
 }  // extern "C"

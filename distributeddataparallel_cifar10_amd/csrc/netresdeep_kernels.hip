@@ -42,15 +42,11 @@ template <bool BF> __device__ __forceinline__ int swz(int key) {
 template <bool BF> __device__ __forceinline__ int rec_off(int rec, int key, int chunk) {
   return ((rec * Rec<BF>::NCH) + (chunk ^ swz<BF>(key))) << 4;
 }
-__device__ __forceinline__ unsigned short bfbits(float f) {
-  return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
 __device__ __forceinline__ unsigned pk2(float a, float b) {
   return (unsigned)bfbits(a) | ((unsigned)bfbits(b) << 16);
 }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *(f32x4*)p = v; }
-__device__ __forceinline__ f32x4 z4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }

@@ -27,6 +27,7 @@
 //
 // Reference semantics: model/resnet.py:5-37 (one shared ResBlock applied 10x, skip after the ReLU),
 // main.py:27-39 (SGD, CrossEntropy mean), BatchNorm2d training statistics + 10 running-stat EMAs per forward.
+#include "pks_ops.h"
 
 namespace dca {
 // stamps build: which forward / backward block gets the detailed stamps (slots 6 / 7)
@@ -47,7 +48,6 @@ constexpr int LMAX = 64 * S;           // logical workgroups (batch <= 64)
 constexpr int NNT = (18 + NW - 1) / NW;  // wgrad tile columns (ci half x tap) per wave
 constexpr int RND_HEAD = 10;           // rounds: 0..9 forward BN, 10 head (fc1 partials), 11..20 backward BN
 constexpr unsigned SPIN_LIMIT = 1u << 17;
-constexpr int RB = 64;                 // bf16 record: 32 channels, 16-B chunks swizzled (rec_chunk)
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 struct Args {
@@ -152,8 +152,7 @@ static_assert(Plan<0>::U_XIN + Plan<0>::XIN_PL <= Plan<0>::U_W1 && Plan<1>::U_XI
 static_assert(Plan<1>::U_SRED <= Plan<1>::U_DYT, "stem-backward staging clear of dyT / xT (last wgrad)");
 static_assert(Plan<1>::SBWD_END <= Plan<1>::U_DYT, "fp32: SRED clear of dyT / xT too");
 
-// ---- helpers ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// ---- helpers (records, st1r, mma3, load_bfrag, xsum_*, lds_barrier: pks_ops.h) -- -----------------------
 __device__ __forceinline__ void pin(float& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void pin(unsigned& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void pin(int& x) { asm volatile("" : "+v"(x)); }
@@ -162,33 +161,6 @@ __device__ __forceinline__ void pin(uint4& x) { asm volatile("" : "+v"(x.x), "+v
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ unsigned short bf_lo(float v, unsigned short hi) {
-  return bfbits(v - __uint_as_float((unsigned)hi << 16));
-}
-// Record layout of the conv operands (inputs XR, weights WT): record r = 32 bf16 channels = four 16-B chunks; chunk
-// q of record r sits at chunk position q ^ 2((r >> 2) & 1).  An MFMA operand read (ds_read_b128, lane 16q + c
-// reads chunk q of record base + c) then touches 16 distinct 16-B bank groups in each of the instruction's four
-// 16-lane groups, for ANY base (an unswizzled record stride cannot: 80-B records conflicted 2-way).
-__device__ __forceinline__ int rec_chunk(int rec, int q) { return ((rec << 6) | (q << 4)) ^ ((rec & 4) << 3); }
-__device__ __forceinline__ int rec_elem(int rec, int ch) { return rec_chunk(rec, ch >> 3) + ((ch & 7) << 1); }
-// one value into channel `ch` of record `rec` (both planes)
-template <int P>
-__device__ __forceinline__ void st1r(char* xr, int plane, int rec, int ch, float v) {
-  const unsigned short hi = bfbits(v);
-  const int o = rec_elem(rec, ch);
-  *(unsigned short*)(xr + o) = hi;
-  if constexpr (P == 1) *(unsigned short*)(xr + plane + o) = bf_lo(v, hi);
-}
-template <int P>
-__device__ __forceinline__ f32x4 mma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl,
-                                      f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
-  if constexpr (P == 1) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
-  }
-  return acc;
-}
 template <int P>
 __device__ __forceinline__ f32x4 mma3s(const s4v& ah, const s4v& al, const s4v& bh, const s4v& bl, f32x4 acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ah, bh, acc, 0, 0, 0);
@@ -199,16 +171,6 @@ __device__ __forceinline__ f32x4 mma3s(const s4v& ah, const s4v& al, const s4v& 
   return acc;
 }
 
-// The B fragments of one conv weight (9 taps, lane 16q + c: record tap*32 + 16h + c, chunk q).  P = 0 keeps them
-// in registers for a whole pass (forward / backward): the conv then reads only its A operand from LDS.
-__device__ __forceinline__ int wrec_off(int h, int lane) {
-  return rec_chunk(16 * h + (lane & 15), lane >> 4);  // + tap * 32 * RB (a multiple of 8 records: same swizzle)
-}
-__device__ __forceinline__ void load_bfrag(const char* wt, int h, int lane, bf16x8 (&bw)[9]) {
-  const char* bb = wt + wrec_off(h, lane);
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) bw[tap] = *(const bf16x8*)(bb + tap * 32 * RB);
-}
 // 3x3 conv of one output row (slice row w), output channels 16h .. 16h+15, on MFMA.  xr: (RS+2) x 18 records,
 // wt: 288 records (tap-major); P=1 reads the lo planes at +XR_PL / +WT_PL and the B operands from LDS, P=0 takes
 // its B operands from registers (bw).
@@ -236,27 +198,6 @@ __device__ __forceinline__ f32x4 conv_row(const char* xr, const char* wt, const 
     acc = mma3<P>(a, al, b, bl, acc);
   }
   return acc;
-}
-
-// a + a[lane ^ 16], then + the same of lane ^ 32: the value every lane of a 16-lane column group ends with, summed in
-// the order of two __shfl_xor steps (bitwise the same; fp addition is commutative) but on the gfx950 cross-row VALU
-// swaps (v_permlane16_swap / v_permlane32_swap) instead of two dependent ds_bpermute LDS round trips
-__device__ __forceinline__ float xsum_rows(float a) {
-  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-  a = __uint_as_float(p[0]) + __uint_as_float(p[1]);
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// sum over the 16 lanes of a row, every lane ending with it: the xor-1 / 2 / 4 / 8 butterfly of __shfl_xor (the same
-// pairings, so bitwise the same sums) on DPP lane moves -- quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
-// row_mirror -- instead of four dependent ds_bpermute round trips
-__device__ __forceinline__ float xsum_row16(float a) {
-  a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0xB1, 0xF, 0xF, false));
-  a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x4E, 0xF, 0xF, false));
-  a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x141, 0xF, 0xF, false));
-  a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x140, 0xF, 0xF, false));
-  return a;
 }
 
 // per-workgroup channel sums of per-thread partials (a, b: channel 16h + c of wave 4h + w), delivered to the

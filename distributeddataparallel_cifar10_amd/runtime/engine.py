@@ -423,6 +423,17 @@ class NetResDeepEngine:
                 self.run(b, k, graph)
         return self.read_loss(reset=True)
 
+    # ---- evaluation -----------------------------------------------------------------------------------------
+    def evaluate(self, data_u8=None, labels=None, indices=None, **kw):
+        """Eval-mode accuracy / loss of the model as trained so far (``runtime/evaluate.py``), issued on the engine's
+        stream, i.e. after every step enqueued before it.  Defaults: the engine's own dataset, ``cfg.dtype``.  Reads
+        the parameters and the BatchNorm running statistics; writes nothing the engine owns."""
+        from .evaluate import evaluate_netresdeep
+        kw.setdefault("dtype", self.cfg.dtype)
+        kw["stream"] = self.lib.dca_engine_stream(self.h)
+        return evaluate_netresdeep(self.model, self.data if data_u8 is None else data_u8,
+                                   self.labels if labels is None else labels, indices, **kw)
+
     # ---- introspection (tests) --------------------------------------------------------------------------
     def region(self, name: str, numel: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a workspace region (synchronises)."""

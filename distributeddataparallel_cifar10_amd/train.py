@@ -62,6 +62,8 @@ class TrainConfig:
     check_sync: int = 0              # >0: assert cross-rank parameter equality every N epochs (and at start)
     allreduce: str = "auto"          # fused engine gradient all-reduce: auto | xgmi (one-shot P2P) | rccl
     fp8: bool = False                # ops engine: fp8 e4m3 forward GEMMs for 1x1 convs / fc (ResNet family)
+    eval: Optional[int] = None       # None: no evaluation; 0: the whole held-out set; N: its first N images
+    eval_only: bool = False          # load `resume`, evaluate, exit (no training, nothing saved)
     extra: dict = field(default_factory=dict)
 
 
@@ -103,12 +105,25 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
                     help="assert parameters are identical on all ranks at start and every N epochs")
     ap.add_argument("--allreduce", default="auto", choices=["auto", "xgmi", "rccl"],
                     help="fused engine gradient all-reduce: one-shot xGMI peer reads (auto inside a node) or RCCL")
+    ap.add_argument("--eval", type=int, nargs="?", const=0, default=None, metavar="N",
+                    help="after every logged epoch (1, 10, 20, ...) and the last one, print the eval-mode accuracy and "
+                         "loss on held-out data: the CIFAR-10 test split (its first N images if N is given), or with "
+                         "--synthetic* N (default 10000) fresh synthetic images of the same kind")
+    ap.add_argument("--eval-only", action="store_true",
+                    help="load --resume, evaluate as --eval does, print the result and exit without training")
     return ap
 
 
 def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConfig:
     learnable = bool(getattr(a, "synthetic_learnable", False))
-    return TrainConfig(epochs=a.epochs, lr=a.lr, batch_size=a.batch_size, data_path=a.data_root or data_path_default,
+    eval_only = bool(getattr(a, "eval_only", False))
+    if eval_only and not a.resume:
+        raise SystemExit("--eval-only requires --resume")
+    n_eval = getattr(a, "eval", None)
+    if n_eval is not None and n_eval < 0:
+        raise SystemExit("--eval N: N must not be negative")
+    return TrainConfig(eval=0 if eval_only and n_eval is None else n_eval, eval_only=eval_only,
+                       epochs=a.epochs, lr=a.lr, batch_size=a.batch_size, data_path=a.data_root or data_path_default,
                        synthetic=a.synthetic or (50000 if learnable else 0), synthetic_learnable=learnable,
                        engine=a.engine, dtype=a.dtype, max_steps=a.max_steps,
                        checkpoint=not a.no_checkpoint, checkpoint_path=a.checkpoint_path, resume=a.resume,
@@ -121,6 +136,61 @@ def load_dataset(cfg: TrainConfig):
     if cfg.synthetic:
         return synthetic_cifar(cfg.synthetic, seed=cfg.seed, learnable="hard" if cfg.synthetic_learnable else False)
     return load_cifar10(cfg.data_path, train=True)
+
+
+def load_eval_dataset(cfg: TrainConfig):
+    """The held-out set of ``--eval``: the real test split, or synthetic images of the training set's kind drawn with
+    another seed (``cfg.seed + 1``); `cfg.eval` = N > 0 keeps the first N."""
+    if cfg.synthetic:
+        return synthetic_cifar(cfg.eval or 10000, seed=cfg.seed + 1,
+                               learnable="hard" if cfg.synthetic_learnable else False)
+    data, labels = load_cifar10(cfg.data_path, train=False)
+    return (data[:cfg.eval], labels[:cfg.eval]) if cfg.eval else (data, labels)
+
+
+def eval_line(epoch: int, accuracy: float, mean_loss: float) -> str:
+    return "Epoch {}, Test accuracy {:.4f}, Test loss {}".format(epoch, accuracy, mean_loss)
+
+
+def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False):
+    """Eval-mode result of `model` on (data, labels), sharded over the ranks of the process group (collective).
+    A ``FusedDDPTrainer`` evaluates with the fused kernel on its engine's stream; `kernel`: a bare NetResDeep on a GPU,
+    the same kernel with no engine; every other model (``FlatBucketDDP``, ``OpsModel``, stock ops) runs as the module in
+    eval mode."""
+    from .parallel.ddp import FusedDDPTrainer
+    from .parallel.flat_ddp import FlatBucketDDP
+    from .runtime.evaluate import evaluate_distributed, evaluate_module
+    if isinstance(model, FusedDDPTrainer):
+        return evaluate_distributed(model.module, data, labels, evaluate=model.engine.evaluate)
+    if kernel:
+        return evaluate_distributed(model, data, labels, dtype=cfg.dtype)
+    fwd = model.module if isinstance(model, FlatBucketDDP) else model  # an OpsModel stays wrapped: its HIP kernels
+    if isinstance(model, FlatBucketDDP) and model.broadcast_buffers:
+        model._broadcast_buffers_now()  # rank 0's buffers, as the wrapper's next forward would install them anyway
+    return evaluate_distributed(unwrap(model), data, labels, sync_bn_stats=False,
+                                evaluate=lambda d, l, i: evaluate_module(fwd, d, l, i))
+
+
+def eval_only(cfg: TrainConfig, device: torch.device, rank: int = 0):
+    """``--eval-only``: build the model, load ``cfg.resume``, evaluate, print; no engine, no training, nothing saved."""
+    from .models.netresdeep import NetResDeep
+    if not cfg.resume:
+        raise ValueError("--eval-only requires --resume")
+    if cfg.model == "resnet50":
+        from .models.resnet50 import resnet50
+        model = resnet50(num_classes=10).to(device)
+    else:
+        model = NetResDeep().to(device)
+    load_checkpoint(model, cfg.resume, strict=True, map_location=device)
+    kind = resolve_engine(cfg, device, model)
+    if kind == "ops":
+        from .ops.models import OpsModel
+        model = OpsModel(model, fp8=cfg.fp8)
+    data, labels = load_eval_dataset(cfg)
+    res = run_eval(model, data, labels, cfg, kernel=kind == "fused")
+    if rank == 0:
+        print("Test accuracy {:.4f}, Test loss {}".format(res.accuracy, res.mean_loss), flush=True)
+    return res
 
 
 FUSED_BATCH_MAX = 64  # csrc/common.h BMAX_LIMIT: per-rank batch the fused NetResDeep engine supports
@@ -182,6 +252,9 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
         model.timing = True  # FlatBucketDDP: record the comm-stream span per step
     if cfg.metrics_json and fused:
         model.engine.comm_time(reset=True)
+    eval_set = load_eval_dataset(cfg) if cfg.eval is not None else None
+    if eval_set is not None:
+        eval_set = (eval_set[0].to(train_loader.device), eval_set[1].to(train_loader.device))
     stack = ExitStack()
     prof = stack.enter_context(_profiler(cfg.profile, train_loader.device)) if cfg.profile else None
     start_time = time.time()
@@ -223,17 +296,23 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
         history.append(mean)
         comm_us, comm_n = _comm_time(model) if cfg.metrics_json else (0.0, 0)
         eng = getattr(model, "engine", None)
+        ev = run_eval(model, *eval_set, cfg) if eval_set is not None and (should_log(epoch) or epoch == cfg.epochs) \
+            else None
+        ev_rec = dict(eval_accuracy=ev.accuracy, eval_loss=ev.mean_loss, eval_images=ev.count) if ev else {}
         mlog.write(epoch=epoch, loss=mean, steps=nsteps, seconds=dt, step_ms=1e3 * dt / max(nsteps, 1),
                    images_per_sec=nsteps * train_loader.batch_size / max(dt, 1e-9),
                    # exposed wait of the reduction kernel's gradient-segment exchanges, summed per step (xGMI)
                    allreduce_us_per_step=(comm_us / comm_n) if comm_n else None,
                    engine=getattr(eng, "kind_name", cfg.engine if not fused else None),
                    dtype=cfg.dtype, fp32_mode=("3xbf16" if getattr(eng, "kind_name", "") == "sliced" else
-                                               "fp32-mfma") if cfg.dtype == "fp32" and fused else None)
+                                               "fp32-mfma") if cfg.dtype == "fp32" and fused else None,
+                   **ev_rec)
         if should_log(epoch):
             print(epoch_line(epoch, mean), flush=True)
             if cfg.checkpoint:
                 save_checkpoint(model, ckpt, rank, meta={"epoch": epoch, "step": global_step})
+        if ev is not None and rank == 0:
+            print(eval_line(epoch, ev.accuracy, ev.mean_loss), flush=True)
         if cfg.check_sync and epoch % cfg.check_sync == 0:
             assert_params_in_sync(unwrap(model))
     total = time.time() - start_time

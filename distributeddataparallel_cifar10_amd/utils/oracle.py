@@ -117,5 +117,23 @@ def reference_step(model, imgs_u8: torch.Tensor, labels: torch.Tensor, lr: float
     return res
 
 
+def reference_eval(model, imgs_u8: torch.Tensor, bf16_operands: bool = False, fc1_bf16: bool = False) -> torch.Tensor:
+    """Eval-mode logits of `model` (BatchNorm on its running statistics), the 10 applications of the shared ResBlock
+    unrolled; `model` is not touched.  The rounding switches are those of ``reference_step``: with both off this is
+    ``model.eval()(normalize_u8(imgs_u8))`` bit for bit; bf16_operands rounds the operands of every conv, fc1_bf16 the
+    fc1 weight (the eval kernel's bf16 mode does both)."""
+    blk = model.resblocks[0]
+    bn = blk.batch_norm
+    with torch.no_grad():
+        cur = F.max_pool2d(torch.relu(_conv(model.conv1, normalize_u8(imgs_u8), bf16_operands)), 2)
+        for _ in range(len(model.resblocks)):
+            y = _conv(blk.conv, cur, bf16_operands)
+            y = F.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
+            cur = torch.relu(y) + cur
+        pooled = F.max_pool2d(cur, 2).view(-1, 8 * 8 * model.n_chans1)
+        h = F.linear(pooled, _bf(model.fc1.weight) if fc1_bf16 else model.fc1.weight, model.fc1.bias)
+        return model.fc2(torch.relu(h))
+
+
 def nchw_to_nhwc(t: torch.Tensor) -> torch.Tensor:
     return t.permute(0, 2, 3, 1).contiguous()

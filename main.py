@@ -23,7 +23,7 @@ import torch.multiprocessing as mp
 from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader
 from distributeddataparallel_cifar10_amd.parallel import dist as pdist
 from distributeddataparallel_cifar10_amd.train import (TrainConfig, add_cli_args, build_model_for_rank,
-                                                       config_from_args, load_dataset)
+                                                       config_from_args, eval_only, load_dataset)
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 from distributeddataparallel_cifar10_amd.utils.gpu import free_gpu_cache  # noqa: F401  (reference main.py:67)
 
@@ -46,6 +46,9 @@ def main(rank, world_size, cfg=None):
     setup(rank, world_size, cfg.backend, cfg.port, cfg.timeout_s)
     try:
         device = torch.device("cuda", rank) if cfg.backend == "nccl" else torch.device("cpu")
+        if cfg.eval_only:  # --eval-only --resume CKPT: the checkpoint's test accuracy, sharded over the ranks
+            eval_only(cfg, device, rank)
+            return
         data, labels = load_dataset(cfg)
         loader = DeviceLoader(data, labels, batch_size=cfg.batch_size, world_size=world_size, rank=rank,
                               device=device, sampler="distributed", seed=0, set_epoch=cfg.set_epoch)

@@ -20,7 +20,7 @@ import torch
 from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader
 from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
 from distributeddataparallel_cifar10_amd.train import TrainConfig, add_cli_args, config_from_args, load_dataset
-from distributeddataparallel_cifar10_amd.train import resolve_engine
+from distributeddataparallel_cifar10_amd.train import eval_only, resolve_engine
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 
 data_path = '../data/CIFAR-10/'  # reference main_no_ddp.py:17
@@ -70,6 +70,9 @@ if __name__ == "__main__":
     _cfg = config_from_args(args, data_path)
     _cfg.checkpoint = False
     print(f"Training on device {device}.")
+    if _cfg.eval_only:  # --eval-only --resume CKPT: the checkpoint's test accuracy; no training
+        eval_only(_cfg, device)
+        raise SystemExit(0)
     if _cfg.model == "resnet50":
         from distributeddataparallel_cifar10_amd.models.resnet50 import resnet50
         torch.manual_seed(_cfg.seed)

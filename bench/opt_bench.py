@@ -1,0 +1,94 @@
+"""Cost of the engine's optimiser pass: microseconds per training step of the plain fused engine (its own SGD inside
+the reduction kernel) against the same engine with ``momentum 0.9 + weight decay 5e-4 + cosine table`` (gradient
+reduced unapplied, then ``k_apply_opt``), sliced engine, bf16 and fp32, batch 32, one GPU.
+
+One process; both engines of a precision live side by side and are timed in interleaved repetitions (plain, optimiser,
+plain, ...), so clock and thermal drift hit both alike.  Each repetition is `--steps` graph-replayed steps between two
+HIP events recorded on the engine's stream; graphs are captured before the first timed repetition.  Reported: median
+and min / max over the repetitions, and the difference of the medians.
+
+    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _engine(dtype, batch, optimizer, data, labels, order):
+    from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
+    from distributeddataparallel_cifar10_amd.runtime.engine import EngineConfig, NetResDeepEngine
+    torch.manual_seed(1234)
+    model = NetResDeep().to(data.device)
+    eng = NetResDeepEngine(model, data, labels, EngineConfig(batch_max=batch, dtype=dtype, persistent=True,
+                                                             optimizer=optimizer), max_indices=len(order))
+    eng.set_indices(order)
+    eng.precapture(batch)
+    return eng
+
+
+def _timed(eng, batch, steps):
+    """Microseconds per step of `steps` graph-replayed steps (HIP events on the engine's stream)."""
+    st = torch.cuda.ExternalStream(eng.lib.dca_engine_stream(eng.h), device=eng.device)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    eng.set_cursor(0)
+    a.record(st)
+    eng.run(batch, steps)
+    b.record(st)
+    b.synchronize()
+    eng.check_errors()
+    return 1e3 * a.elapsed_time(b) / steps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--steps", type=int, default=320)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--warmup", type=int, default=64)
+    a = ap.parse_args(argv)
+    from distributeddataparallel_cifar10_amd.data.synthetic import synthetic_cifar
+    from distributeddataparallel_cifar10_amd.runtime.engine import OptimizerConfig
+    from distributeddataparallel_cifar10_amd.utils.schedule import lr_table
+    dev = torch.device("cuda", 0)
+    data, labels = synthetic_cifar(16384, seed=0)
+    data, labels = data.to(dev), labels.to(dev)
+    order = np.resize(np.arange(16384, dtype=np.int32), max(a.steps, a.warmup) * a.batch)
+    total = a.warmup + a.steps * a.reps
+    out = {}
+    for dtype in ("bf16", "fp32"):
+        opt = OptimizerConfig(momentum=0.9, weight_decay=5e-4, lr_table=lr_table("cosine", 1e-2, total, warmup_steps=32))
+        engines = {"plain": _engine(dtype, a.batch, None, data, labels, order),
+                   "optimizer": _engine(dtype, a.batch, opt, data, labels, order)}
+        for eng in engines.values():
+            _timed(eng, a.batch, a.warmup)
+        us = {k: [] for k in engines}
+        for _ in range(a.reps):
+            for k, eng in engines.items():  # interleaved
+                us[k].append(_timed(eng, a.batch, a.steps))
+        for k, eng in engines.items():
+            loss, _ = eng.read_loss(reset=True)
+            assert np.isfinite(loss), (dtype, k, loss)
+            eng.close()
+        med = {k: statistics.median(v) for k, v in us.items()}
+        out[dtype] = {"plain_us": round(med["plain"], 2), "optimizer_us": round(med["optimizer"], 2),
+                      "delta_us": round(med["optimizer"] - med["plain"], 2)}
+        for k, v in us.items():
+            print(f"{dtype} {k:9s} us/step: median {med[k]:.2f}  min {min(v):.2f}  max {max(v):.2f}  "
+                  f"reps {' '.join(f'{x:.2f}' for x in v)}", flush=True)
+        print(f"{dtype} optimiser pass costs {med['optimizer'] - med['plain']:+.2f} us/step "
+              f"({100 * (med['optimizer'] / med['plain'] - 1):+.1f} %)", flush=True)
+    print(json.dumps({"bench": "opt_bench", "engine": "sliced", "batch": a.batch, "steps": a.steps, "reps": a.reps,
+                      **out}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -10,6 +10,7 @@
 //     which replaces DDP's per-forward buffer broadcast (CC4) at zero extra collective latency.
 #include <rccl/rccl.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "netresdeep_kernels.hip"
+#include "optimizer.h"
 #include "xgmi_allreduce.hip"
 #include "netresdeep_pks.hip"
 #include "netresdeep_eval.hip"
@@ -133,6 +135,12 @@ struct Engine {
   void (*kbwd)(Ctx, int) = nullptr;
   void (*kred)(Ctx, int, int) = nullptr;
   void (*kapply)(Ctx, int) = nullptr;
+  // optimiser pass (optimizer.hip; dca_engine_set_optimizer).  Off: every step applies its own plain SGD as before.
+  // On: the step takes the "split" form -- gradient reduced (and all-reduced) into cx.grads unapplied, then k_apply_opt
+  bool opt_on = false;
+  OptDev* optdev = nullptr;     // device copy: hyper-parameters, step counter, ticket
+  OptDev opt{};                 // host mirror of the hyper-parameters (step / ticket live on the device only)
+  float* lr_table = nullptr;    // device learning-rate table (owned)
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -282,6 +290,30 @@ static int enqueue_xgmi_sgd(Engine* e, const Ctx& cx) {
   return 0;
 }
 
+// Optimiser mode, comm_mode 2: the same one-shot all-reduce without the update -- the summed gradient (CC4 tail
+// included) lands in cx.grads, k_apply_opt follows
+static int enqueue_xgmi_sum(Engine* e, const Ctx& cx) {
+  if (!e->peers_open) {
+    g_err = "xGMI all-reduce: peers not mapped (call dca_engine_ipc_open first)";
+    return -1;
+  }
+  if (e->bf)
+    hipLaunchKernelGGL(xg::k_xgmi_ar_sgd<true>, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, e->peers,
+                       (const float*)cx.grads, cx.grads, e->qa.err + 1, 0, e->ar_deadline);
+  else
+    hipLaunchKernelGGL(xg::k_xgmi_ar_sgd<false>, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, e->peers,
+                       (const float*)cx.grads, cx.grads, e->qa.err + 1, 0, e->ar_deadline);
+  HIPCK(hipGetLastError());
+  return 0;
+}
+
+// The optimiser pass over the flat buffer (momentum, weight decay, the step's learning rate; derived weight copies;
+// CC4 base) -- in place of the step's own SGD when an optimiser is set.
+static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
+  HIPCK(launch_apply_opt(e->bf, cx, e->optdev, e->st));
+  return 0;
+}
+
 // Persistent path: the sliced step kernel, then ONE kernel for reduction + all-reduce + SGD (mode: see
 // k_pks_reduce_ar).  `part`: 0 = the whole step; 1 = compute up to (not including) the gradient all-reduce;
 // 2 = what follows it (averaging SGD + CC4 base).  Parts 1/2 exist for comm_mode 1, where the host runs the
@@ -330,7 +362,7 @@ static int reduce_grid(const Engine* e, int nred_plus) {
 // step's ready wait is bounded by the exchange deadline (netresdeep_pks.hip wait_ready), and the form is covered by a
 // two-rank shared-device test (tests/test_ddp_engine_gpu.py::test_xgmi_prologue_two_ranks_one_gpu).
 static bool prologue_ok(const Engine* e, int B) {
-  if (!e->persistent || !e->prologue) return false;
+  if (!e->persistent || !e->prologue || e->opt_on) return false;  // (optimiser: the pass sits between the steps)
   if (e->comm_on && e->in.comm_mode != 2) return false;
   if (!fc_in_step_for(e, B)) return false;
   return pks_live(B) + std::max(pks::N_FCW, pks::prologue_segments(seg_ch(e))) <= share_budget(e);
@@ -354,7 +386,7 @@ static int enqueue_pks_step(Engine* e, int B, int s, bool prev) {
   ra.peers = e->peers;
   ra.err = e->qa.err + 1;
   ra.deadline = e->ar_deadline;
-  ra.mode = !multi ? 0 : (xgmi ? 2 : 1);
+  ra.mode = e->opt_on ? 1 : (!multi ? 0 : (xgmi ? 2 : 1));  // optimiser: gradient only (fc workers included)
   const bool fc = fc_in_step_for(e, B);
   ra.fc_in_step = pks::ra_flags(fc, prev, s, 0);
   ra.seg_ch = seg_ch(e);
@@ -386,7 +418,7 @@ static int enqueue_pks_reduce(Engine* e, int B, int chunk, int part) {
     ra.peers = e->peers;
     ra.err = e->qa.err + 1;
     ra.deadline = e->ar_deadline;
-    ra.mode = !multi ? 0 : (xgmi ? 2 : 1);
+    ra.mode = e->opt_on ? 1 : (!multi ? 0 : (xgmi ? 2 : 1));
     const bool fc = fc_in_step_for(e, B);
     ra.fc_in_step = pks::ra_flags(fc, false, 0, chunk);
     ra.seg_ch = seg_ch(e);
@@ -402,7 +434,12 @@ static int enqueue_pks_reduce(Engine* e, int B, int chunk, int part) {
     else
       hipLaunchKernelGGL(pks::k_pks_reduce_ar<0>, rgrid, dim3(256), lds, e->st, cx, e->qa, B * pks::S, ra);
   }
-  if (multi && !xgmi) {  // RCCL (comm_mode 0, captured) or the host (comm_mode 1, between parts 1 and 2)
+  if (e->opt_on) {  // split form: the collective on the unapplied gradient, then the optimiser pass
+    if (multi && xgmi && part == 0 && enqueue_xgmi_sum(e, cx)) return -1;
+    if (multi && !xgmi && part == 0)
+      NCCK(ncclAllReduce(cx.grads, cx.grads, FLAT_N, ncclFloat32, ncclSum, e->comm, e->st));
+    if (part != 1 && enqueue_apply_opt(e, cx)) return -1;
+  } else if (multi && !xgmi) {  // RCCL (comm_mode 0, captured) or the host (comm_mode 1, between parts 1 and 2)
     if (part == 0) NCCK(ncclAllReduce(cx.grads, cx.grads, FLAT_N, ncclFloat32, ncclSum, e->comm, e->st));
     if (part != 1) hipLaunchKernelGGL(e->kapply, dim3(64), dim3(NT), 0, e->st, cx, 1);
   }
@@ -435,7 +472,9 @@ static int enqueue_step(Engine* e, int B, int part) {
   if (e->persistent) return enqueue_step_persistent(e, B, part);
   Ctx cx = e->base;
   cx.B = B;
+  if (e->opt_on) cx.fuse_sgd = 0;  // k_reduce writes the gradient only; k_apply_opt applies it
   if (part == 2) {  // external all-reduce done: averaging SGD + CC4 base
+    if (e->opt_on) return enqueue_apply_opt(e, cx);
     hipLaunchKernelGGL(e->kapply, dim3(64), dim3(NT), 0, e->st, cx, 1);
     HIPCK(hipGetLastError());
     return 0;
@@ -460,6 +499,21 @@ static int enqueue_step(Engine* e, int B, int part) {
   }
   const int nother = cx.fuse_sgd ? 64 : 0;
   hipLaunchKernelGGL(e->kred, dim3(N_TRUNK_RED_WG + N_STEM_RED_WG + nother + 1), blk, 0, e->st, cx, nslab, nparts);
+  if (e->opt_on) {  // the collective on the unapplied gradient, then the optimiser pass in place of kapply
+    if (e->comm_on && part == 0 && e->in.comm_mode == 2) {
+      if (enqueue_xgmi_sum(e, cx)) return -1;
+    } else if (e->comm_on && part == 0) {
+      HIPCK(hipEventRecord(e->evB, e->st));
+      HIPCK(hipStreamWaitEvent(e->cst, e->evB, 0));
+      NCCK(ncclAllReduce(cx.grads + OFF_CONVW, cx.grads + OFF_CONVW, FLAT_N - OFF_CONVW, ncclFloat32, ncclSum, e->comm,
+                         e->cst));
+      HIPCK(hipEventRecord(e->evC, e->cst));
+      HIPCK(hipStreamWaitEvent(e->st, e->evC, 0));
+    }
+    if (part != 1) return enqueue_apply_opt(e, cx);
+    HIPCK(hipGetLastError());
+    return 0;
+  }
   if (e->comm_on && part == 0 && e->in.comm_mode == 2) return enqueue_xgmi_sgd(e, cx);
   if (e->comm_on && part == 0) {
     HIPCK(hipEventRecord(e->evB, e->st));
@@ -653,6 +707,8 @@ static void engine_free(Engine* e) {
       (void)hipIpcCloseMemHandle(e->peers.base[q]);
   if (e->xregion) (void)hipFree(e->xregion);
   if (e->wsp) (void)hipFree(e->wsp);
+  if (e->optdev) (void)hipFree(e->optdev);
+  if (e->lr_table) (void)hipFree(e->lr_table);
   if (e->indices) (void)hipFree(e->indices);
   if (e->err_host) (void)hipHostFree(e->err_host);
   for (auto& ev : e->chk_ev)
@@ -1161,6 +1217,109 @@ int dca_engine_set_shared_device(void* h, int n) {
   for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
   e->graphs.clear();
   e->shared_device = n > 1 ? n : 0;
+  return 0;
+}
+
+// Drop the captured step graphs (the step's kernel chain is about to change).  The stream must be idle.
+static void drop_graphs(Engine* e) {
+  for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
+  e->graphs.clear();
+}
+
+// Optimiser of the fused step: SGD with momentum `mu` and weight decay `wd` (optimizer.hip).  `momentum_buf`: flat
+// fp32 [FLAT_ALLOC] device buffer owned by the caller (layout of params / grads; the caller zeroes or restores it);
+// null turns the optimiser off again (the step's own plain SGD).  The learning rate is the engine's constant one until
+// dca_engine_set_lr_table installs a table; the step counter starts at 0.  Turning the mode on or off drops the
+// captured graphs (a different kernel chain); new mu / wd values on an engine already in optimiser mode reach the
+// captured graphs as they are (device memory).  Synchronous.
+int dca_engine_set_optimizer(void* h, float* momentum_buf, float mu, float wd) {
+  Engine* e = (Engine*)h;
+  if (momentum_buf && (!(mu >= 0.f) || !(wd >= 0.f))) {
+    g_err = "set_optimizer: momentum and weight decay must not be negative";
+    return -1;
+  }
+  if (momentum_buf && ((uintptr_t)momentum_buf % 16)) {
+    g_err = "set_optimizer: the momentum buffer must be 16-byte aligned";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  const bool on = momentum_buf != nullptr;
+  if (on != e->opt_on) drop_graphs(e);
+  e->opt_on = false;  // (on again below, once the device block is complete)
+  if (!on) return 0;
+  if (e->optdev == nullptr) {  // first use: step 0, ticket 0, no table
+    e->opt = dca::OptDev{};
+    e->opt.lr_const = e->in.lr;
+    e->opt.buf = momentum_buf;
+    e->opt.mu = mu;
+    e->opt.wd = wd;
+    dca::OptDev* d = nullptr;
+    HIPCK(hipMalloc((void**)&d, sizeof(dca::OptDev)));
+    if (hipMemcpy(d, &e->opt, sizeof(dca::OptDev), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      g_err = "set_optimizer: copy failed";
+      return -1;
+    }
+    e->optdev = d;
+  } else {  // keep the device's step counter
+    e->opt.buf = momentum_buf;
+    e->opt.mu = mu;
+    e->opt.wd = wd;
+    HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
+  }
+  e->opt_on = true;
+  return 0;
+}
+
+// Per-step learning rates of the optimiser pass: step k uses values[min(k, n - 1)]; n = 0 returns to the engine's
+// constant learning rate.  Captured graphs pick the new table up without re-capture.  Synchronous.
+int dca_engine_set_lr_table(void* h, const float* values, int n) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on) {
+    g_err = "set_lr_table: no optimiser set (dca_engine_set_optimizer first)";
+    return -1;
+  }
+  if (n < 0 || (n > 0 && !values)) {
+    g_err = "set_lr_table: bad table";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  float* tab = nullptr;
+  if (n > 0) {
+    HIPCK(hipMalloc((void**)&tab, sizeof(float) * (size_t)n));
+    if (hipMemcpy(tab, values, sizeof(float) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(tab);
+      g_err = "set_lr_table: copy failed";
+      return -1;
+    }
+  }
+  float* old = e->lr_table;
+  e->lr_table = tab;
+  e->opt.lr_table = tab;
+  e->opt.n_table = n;
+  HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
+  if (old) (void)hipFree(old);
+  return 0;
+}
+
+// The optimiser pass's own step counter (it indexes the learning-rate table; unlike the loss step count it is never
+// reset by a loss read).  set = 0: *value <- counter; set = 1: counter <- *value (resume).  Synchronous.
+int dca_engine_opt_step(void* h, int set, int* value) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on || !value) {
+    g_err = "opt_step: no optimiser set";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  if (set) {
+    if (*value < 0) {
+      g_err = "opt_step: negative step";
+      return -1;
+    }
+    HIPCK(hipMemcpy(&e->optdev->step, value, sizeof(int), hipMemcpyHostToDevice));
+  } else {
+    HIPCK(hipMemcpy(value, &e->optdev->step, sizeof(int), hipMemcpyDeviceToHost));
+  }
   return 0;
 }
 

@@ -1,0 +1,77 @@
+// The optimiser pass of the NetResDeep engine: SGD with momentum and weight decay on a per-step learning rate, as
+// one kernel over the flat parameter buffer.  It runs after the step's gradient has been reduced (and, world size
+// > 1, all-reduced) into cx.grads WITHOUT being applied: the sliced engine's mode 1, the multi-kernel engine's
+// fuse_sgd = 0, k_xgmi_ar_sgd with sgd = 0 (engine.hip, "split" step form).
+//
+// Arithmetic per element, three fused multiply-adds in this order (g: the summed gradient, p: the parameter):
+//   d   = fmaf(wd, p, g * inv_ws)      averaged gradient + weight decay
+//   buf = fmaf(mu, buf, d)             momentum buffer (starts at zero: the first update equals d)
+//   p   = fmaf(-lr, buf, p)
+// i.e. torch.optim.SGD(momentum = mu, weight_decay = wd), dampening 0, decay on all nine tensors.  With mu = wd = 0
+// and inv_ws = 1 it is the fused step's fmaf(-lr, g, p) exactly (d = g, buf = g).
+//
+// The hyper-parameters live in device memory (OptDev), not in the kernel arguments, so a captured step graph picks
+// up a new learning-rate table, momentum or decay without re-capture.  The learning rate of a launch is
+// lr_table[min(step, n_table - 1)] (lr_const without a table); `step` is the pass's own device counter (the
+// engine's step_count is cleared at every epoch's loss read) and advances once per launch, by the workgroup that
+// takes the last ticket -- every workgroup reads `step` before it takes its ticket.
+// A translation unit of its own (see optimizer.h); derive_param comes from netresdeep_kernels.hip.
+#include "netresdeep_kernels.hip"
+#include "optimizer.h"
+
+namespace dca {
+
+constexpr int OPT_V4 = OFF_RS / 4;                  // 19019 float4 (every tensor starts 16-byte aligned)
+constexpr int OPT_NB = (OPT_V4 + NT - 1) / NT;      // 75 workgroups, one float4 per thread
+static_assert(OFF_RS % 4 == 0, "the parameter range must be float4 granular");
+
+template <bool BF>
+__global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
+  __shared__ float s_lr;
+  __shared__ int s_step;
+  const int t = threadIdx.x, v = blockIdx.x * NT + t;
+  if (t == 0) {
+    const int st = __hip_atomic_load(&od->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int n = od->n_table;
+    s_step = st;
+    s_lr = n > 0 ? od->lr_table[st < n - 1 ? (st < 0 ? 0 : st) : n - 1] : od->lr_const;
+  }
+  const float mu = od->mu, wd = od->wd;
+  float* mbuf = od->buf;
+  __syncthreads();
+  const float lr = s_lr;
+  if (v < OPT_V4) {
+    const int e0 = 4 * v;
+    const f32x4 g = *(const f32x4*)(cx.grads + e0);
+    f32x4 p = *(const f32x4*)(cx.params + e0);
+    f32x4 m = *(const f32x4*)(mbuf + e0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float d = __builtin_fmaf(wd, p[k], g[k] * cx.inv_ws);
+      m[k] = __builtin_fmaf(mu, m[k], d);
+      p[k] = __builtin_fmaf(-lr, m[k], p[k]);
+    }
+    *(f32x4*)(mbuf + e0) = m;
+    *(f32x4*)(cx.params + e0) = p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) derive_param<BF>(cx, e0 + k, p[k]);
+  }
+  // CC4: rank 0's running statistics (the tail of the all-reduced buffer) become every rank's base
+  if (cx.ws > 1 && v < 64) cx.rs_base[v] = cx.grads[OFF_RS + v];
+  if (t == 0) {  // the last workgroup to arrive advances the step (all have read it: their tickets are taken after)
+    const unsigned prev = __hip_atomic_fetch_add(&od->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == gridDim.x - 1) {
+      __hip_atomic_store(&od->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int st = s_step;
+      __hip_atomic_store(&od->step, st < 0x7fffffff ? st + 1 : st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+hipError_t launch_apply_opt(bool bf, const Ctx& cx, OptDev* od, hipStream_t st) {
+  if (bf) hipLaunchKernelGGL(k_apply_opt<true>, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
+  else hipLaunchKernelGGL(k_apply_opt<false>, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
+  return hipGetLastError();
+}
+
+}  // namespace dca

@@ -14,7 +14,7 @@ import ctypes
 import os
 import warnings
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -128,6 +128,17 @@ def max_sliced_batch(per_cu: int, ncu: int, n_share: int = 1, full_device: bool 
 
 
 @dataclass
+class OptimizerConfig:
+    """SGD with momentum and weight decay on a per-step learning rate, run by the engine's optimiser pass
+    (``csrc/optimizer.hip``) after each step's gradient reduction -- torch ``SGD(momentum, weight_decay)`` with
+    dampening 0 and decay on every tensor.  ``lr_table``: one learning rate per optimiser step (the last entry holds
+    beyond its end; ``utils/schedule.py`` builds them); ``None``: the engine's constant ``lr``."""
+    momentum: float = 0.0
+    weight_decay: float = 0.0
+    lr_table: Optional[Sequence[float]] = None
+
+
+@dataclass
 class EngineConfig:
     batch_max: int = 32
     lr: float = 1e-2
@@ -152,6 +163,8 @@ class EngineConfig:
     full_device: bool = False    # automatic engine choice on a device this process has to itself: the sliced step may
                                  # hold every CU (no slack CU), so batch 64 fits; a batch or a device that still does
                                  # not fit falls back to the multi-kernel engine (main_no_ddp.py)
+    optimizer: Optional[OptimizerConfig] = None  # None: the step's own plain SGD(lr) (the default path, unchanged);
+                                 # set: every step reduces its gradient unapplied and the optimiser pass applies it
 
 
 class NetResDeepEngine:
@@ -224,6 +237,98 @@ class NetResDeepEngine:
         self.kind_name = KIND_NAMES.get(self.kind, str(self.kind))
         self.derive()
         self._n_indices = 0
+        self.momentum = None  # flat fp32 momentum buffer (optimiser mode), laid out like `flat` and `grads`
+        if cfg.optimizer is not None:
+            self.set_optimizer(cfg.optimizer)
+
+    # ---- optimiser pass -------------------------------------------------------------------------------------
+    def set_optimizer(self, opt: Optional[OptimizerConfig]) -> None:
+        """Turn the optimiser pass on (momentum buffer zeroed on first use, step counter 0) or, ``None``, off again.
+        Meant to be fixed before the first step; switching the mode later drops the captured step graphs."""
+        if opt is None:
+            native.check(self.lib.dca_engine_set_optimizer(self.h, None, 0.0, 0.0), "dca_engine_set_optimizer")
+            self.cfg.optimizer = None
+            return
+        if opt.momentum < 0 or opt.weight_decay < 0:
+            raise ValueError("momentum and weight_decay must not be negative")
+        if self.momentum is None:
+            self.momentum = torch.zeros(FLAT_ALLOC, dtype=torch.float32, device=self.device)
+            torch.cuda.synchronize(self.device)
+        native.check(self.lib.dca_engine_set_optimizer(self.h, self.momentum.data_ptr(), float(opt.momentum),
+                                                       float(opt.weight_decay)), "dca_engine_set_optimizer")
+        self.cfg.optimizer = opt
+        if opt.lr_table is not None:
+            self.set_lr_table(opt.lr_table)
+
+    def set_lr_table(self, values) -> None:
+        """Per-step learning rates: optimiser step k uses ``values[min(k, len - 1)]``; an empty table returns to the
+        constant ``cfg.lr``.  Captured step graphs pick it up without re-capture (the table lives in device memory)."""
+        self._need_optimizer()
+        tab = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1))
+        if tab.size and not np.all(np.isfinite(tab)):
+            raise ValueError("learning-rate table holds a non-finite value")
+        native.check(self.lib.dca_engine_set_lr_table(self.h, tab.ctypes.data, int(tab.size)),
+                     "dca_engine_set_lr_table")
+
+    def optimizer_step(self) -> int:
+        """Optimiser steps taken so far (the device counter that indexes the learning-rate table).  Synchronises."""
+        self._need_optimizer()
+        v = ctypes.c_int()
+        native.check(self.lib.dca_engine_opt_step(self.h, 0, ctypes.byref(v)), "dca_engine_opt_step")
+        return int(v.value)
+
+    def optimizer_state(self) -> dict:
+        """``{"step": int, "momentum_buffer": {parameter name: tensor}}``; the tensors are views of the flat momentum
+        buffer through ``LAYOUT`` (clone them to keep a snapshot).  Synchronises."""
+        step = self.optimizer_step()
+        bufs = {name: self.momentum[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
+        return {"step": step, "momentum_buffer": bufs}
+
+    def load_optimizer_state(self, state: dict) -> None:
+        """Restore ``optimizer_state()`` output (tensors on any device)."""
+        self._need_optimizer()
+        bufs = state["momentum_buffer"]
+        if set(bufs) != set(LAYOUT):
+            raise ValueError(f"momentum buffers must cover exactly {sorted(LAYOUT)}")
+        self.sync()
+        with torch.no_grad():
+            for name, (off, shape) in LAYOUT.items():
+                t = bufs[name]
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+                self.momentum[off:off + t.numel()].copy_(t.detach().to(self.device, torch.float32).reshape(-1))
+        torch.cuda.synchronize(self.device)
+        v = ctypes.c_int(int(state["step"]))
+        native.check(self.lib.dca_engine_opt_step(self.h, 1, ctypes.byref(v)), "dca_engine_opt_step")
+
+    # ---- carried step state ---------------------------------------------------------------------------------
+    def step_state(self) -> dict:
+        """What the step kernels carry from one step to the next besides the model and optimiser state: the last
+        step's per-block BatchNorm batch statistics (``STATS`` [10][32] (mean, invstd)), which the sliced step uses as
+        the shift of the next step's variance sums, and (sliced engine) the device step epoch -- at epoch 0 there is
+        no previous step, so the first step of a fresh engine runs unshifted and rounds its statistics differently.
+        Restoring both makes a resumed run bitwise the uninterrupted one."""
+        state = {"bn_batch_stats": self.region("STATS", 640).cpu()}
+        if self.kind_name == "sliced":
+            state["epoch"] = self.epoch()
+        return state
+
+    def load_step_state(self, state: dict) -> None:
+        t = state["bn_batch_stats"].detach().to(self.device, torch.float32).contiguous()
+        if t.numel() != 640:
+            raise ValueError("bn_batch_stats must hold [10][32] (mean, invstd) pairs")
+        self.sync()
+        # (over xGMI with peers, seeding the epoch is a collective that also seeds the exchange flags -- set_epoch --
+        # and is left out here: such a resume continues correctly, but from epoch 0, i.e. not bitwise)
+        if "epoch" in state and self.kind_name == "sliced" and not (self.cfg.comm == "xgmi" and self.cfg.world_size > 1):
+            self.set_epoch(int(state["epoch"]))
+        torch.cuda.synchronize(self.device)
+        _copy_to_ptr(self.lib.dca_engine_region(self.h, b"STATS"), t)
+        torch.cuda.synchronize(self.device)
+
+    def _need_optimizer(self) -> None:
+        if self.cfg.optimizer is None:
+            raise RuntimeError("no optimiser set: EngineConfig(optimizer=OptimizerConfig(...)) or set_optimizer()")
 
     def set_shared_device(self, n: int) -> None:
         """Sliced engine, xGMI: ``n`` ranks share one device (shared-GPU rehearsal; the largest count over all
@@ -477,6 +582,15 @@ def _copy_from_ptr(out: torch.Tensor, ptr: int) -> None:
     hip = _hip_runtime()
     nbytes = out.numel() * out.element_size()
     rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 3)
+    if rc != 0:
+        raise RuntimeError(f"hipMemcpy failed: {rc}")
+
+
+def _copy_to_ptr(ptr: int, src: torch.Tensor) -> None:
+    """Copy src.numel() elements of device tensor `src` to raw device pointer `ptr` (same device)."""
+    hip = _hip_runtime()
+    nbytes = src.numel() * src.element_size()
+    rc = hip.hipMemcpy(ctypes.c_void_p(ptr), ctypes.c_void_p(src.data_ptr()), ctypes.c_size_t(nbytes), 3)
     if rc != 0:
         raise RuntimeError(f"hipMemcpy failed: {rc}")
 

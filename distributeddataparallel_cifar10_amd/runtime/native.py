@@ -60,6 +60,9 @@ def _declare(lib):
     lib.dca_engine_epoch.argtypes = [c_void_p, ctypes.POINTER(c_int)]
     lib.dca_engine_fc_in_step.argtypes = [c_void_p, c_int]
     lib.dca_engine_prologue.argtypes = [c_void_p, c_int]
+    lib.dca_engine_set_optimizer.argtypes = [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float]
+    lib.dca_engine_set_lr_table.argtypes = [c_void_p, c_void_p, c_int]
+    lib.dca_engine_opt_step.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]
     lib.dca_eval_netresdeep.argtypes = [c_void_p, c_void_p]  # DcaEvalArgs*, hipStream_t (runtime/evaluate.py)
     lib.dca_engine_comm_time.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong),
                                          c_int]

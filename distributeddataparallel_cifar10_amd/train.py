@@ -14,7 +14,8 @@ the same stdout lines -- while the step itself runs on the MI355X-native path:
 * ``engine="torch"``: stock PyTorch ops + ``FlatBucketDDP`` (generic path; CPU / gloo; any model).
 
 Options beyond the reference (all off by default): max_steps (per epoch), synthetic data, resume, metrics JSON,
-fault injection (``fail_at_step``), process-group timeout, set_epoch reshuffling, bf16/fp32 engine precision.
+fault injection (``fail_at_step``), process-group timeout, set_epoch reshuffling, bf16/fp32 engine precision,
+momentum / weight decay / a per-step learning-rate schedule (``optimizer_active``; one table drives every engine).
 """
 from __future__ import annotations
 
@@ -64,6 +65,13 @@ class TrainConfig:
     fp8: bool = False                # ops engine: fp8 e4m3 forward GEMMs for 1x1 convs / fc (ResNet family)
     eval: Optional[int] = None       # None: no evaluation; 0: the whole held-out set; N: its first N images
     eval_only: bool = False          # load `resume`, evaluate, exit (no training, nothing saved)
+    momentum: float = 0.0            # SGD momentum (dampening 0); with the fields below: see optimizer_active()
+    weight_decay: float = 0.0        # L2 decay on every parameter tensor (torch's default grouping)
+    lr_schedule: Optional[str] = None  # None (constant `lr`, no table) | constant | step | cosine
+    lr_warmup_steps: int = 0         # linear warm-up over the first N optimiser steps
+    lr_min: float = 0.0              # cosine: the final learning rate
+    lr_step_epochs: Optional[int] = None  # step: decay every N epochs ...
+    lr_gamma: float = 0.1            # ... by this factor
     extra: dict = field(default_factory=dict)
 
 
@@ -111,6 +119,14 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
                          "--synthetic* N (default 10000) fresh synthetic images of the same kind")
     ap.add_argument("--eval-only", action="store_true",
                     help="load --resume, evaluate as --eval does, print the result and exit without training")
+    ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (dampening 0); default 0: plain SGD")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="L2 weight decay on every parameter tensor")
+    ap.add_argument("--lr-schedule", default=None, choices=["constant", "step", "cosine"],
+                    help="per-step learning-rate schedule over epochs x steps-per-epoch steps (default: constant --lr)")
+    ap.add_argument("--lr-warmup-steps", type=int, default=0, help="linear warm-up over the first N steps")
+    ap.add_argument("--lr-min", type=float, default=0.0, help="cosine schedule: the final learning rate")
+    ap.add_argument("--lr-step-epochs", type=int, default=None, help="step schedule: decay every N epochs")
+    ap.add_argument("--lr-gamma", type=float, default=0.1, help="step schedule: decay factor")
     return ap
 
 
@@ -129,7 +145,115 @@ def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConf
                        checkpoint=not a.no_checkpoint, checkpoint_path=a.checkpoint_path, resume=a.resume,
                        metrics_json=a.metrics_json, seed=a.seed, set_epoch=a.set_epoch, fail_at_step=a.fail_at_step,
                        backend=a.backend, port=a.port, timeout_s=a.timeout, model=a.model, bucket_mb=a.bucket_mb,
-                       profile=a.profile, check_sync=a.check_sync, allreduce=a.allreduce, fp8=a.fp8)
+                       profile=a.profile, check_sync=a.check_sync, allreduce=a.allreduce, fp8=a.fp8,
+                       momentum=getattr(a, "momentum", 0.0), weight_decay=getattr(a, "weight_decay", 0.0),
+                       lr_schedule=getattr(a, "lr_schedule", None), lr_warmup_steps=getattr(a, "lr_warmup_steps", 0),
+                       lr_min=getattr(a, "lr_min", 0.0), lr_step_epochs=getattr(a, "lr_step_epochs", None),
+                       lr_gamma=getattr(a, "lr_gamma", 0.1))
+
+
+def optimizer_active(cfg: TrainConfig) -> bool:
+    """Whether any optimiser option beyond the reference's SGD(lr) is on.  Off (the default): the fused engine runs
+    its own fused SGD (``optimizer=None``) and the other engines build FlatSGD(model, lr) / torch.optim.SGD(lr)."""
+    return bool(cfg.momentum or cfg.weight_decay or cfg.lr_schedule is not None or cfg.lr_warmup_steps)
+
+
+def steps_per_epoch_of(cfg: TrainConfig, n_batches: int) -> int:
+    return min(n_batches, cfg.max_steps) if cfg.max_steps else n_batches
+
+
+def lr_table_for(cfg: TrainConfig, n_batches: int):
+    """The run's learning-rate table (one value per optimiser step, epochs x steps per epoch), or None when no
+    optimiser option is on.  The same table drives every engine."""
+    if not optimizer_active(cfg):
+        return None
+    from .utils.schedule import lr_table
+    spe = steps_per_epoch_of(cfg, n_batches)
+    kind = cfg.lr_schedule or "constant"
+    if kind == "step" and not cfg.lr_step_epochs:
+        raise ValueError("--lr-schedule step needs --lr-step-epochs")
+    return lr_table(kind, cfg.lr, max(cfg.epochs * spe, 1), warmup_steps=cfg.lr_warmup_steps, min_lr=cfg.lr_min,
+                    step_size=cfg.lr_step_epochs * spe if cfg.lr_step_epochs else None, gamma=cfg.lr_gamma)
+
+
+def engine_optimizer(cfg: TrainConfig, n_batches: int):
+    """The fused engine's ``OptimizerConfig`` for `cfg` (None when no optimiser option is on)."""
+    table = lr_table_for(cfg, n_batches)
+    if table is None:
+        return None
+    from .runtime.engine import OptimizerConfig
+    return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table)
+
+
+def optim_path(checkpoint_path: str) -> str:
+    return f"{checkpoint_path}.optim.pt"
+
+
+def _momentum_buffers(model, optimizer) -> dict:
+    """{parameter name: momentum buffer} of the generic engines' optimiser (tensors absent before the first step)."""
+    from .parallel.flat_ddp import FlatSGD
+    named = dict(unwrap(model).named_parameters())
+    if isinstance(optimizer, FlatSGD):
+        buf, flat = optimizer._buf, optimizer.ddp.flat
+        if buf is None:
+            return {}
+        out = {}
+        for name, p in named.items():
+            off = (p.data_ptr() - flat.data_ptr()) // flat.element_size()
+            out[name] = buf[off:off + p.numel()].view(p.shape)
+        return out
+    return {name: optimizer.state[p]["momentum_buffer"] for name, p in named.items()
+            if optimizer.state.get(p, {}).get("momentum_buffer") is not None}
+
+
+def save_optimizer_state(model, optimizer, path: str, rank: int, step: int) -> None:
+    """Rank 0 writes ``<checkpoint>.optim.pt``: ``{"step", "momentum_buffer": {name: CPU tensor}}`` (atomically)."""
+    from .parallel.ddp import FusedDDPTrainer
+    if rank != 0:
+        return
+    extra = {}
+    if isinstance(model, FusedDDPTrainer):
+        bufs = model.engine.optimizer_state()["momentum_buffer"]
+        extra["engine"] = model.engine.step_state()  # the step kernels' carried BN shifts (bitwise resume)
+    else:
+        bufs = _momentum_buffers(model, optimizer)
+    state = {"step": int(step), "momentum_buffer": {k: v.detach().to("cpu", copy=True) for k, v in bufs.items()},
+             **extra}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = f"{optim_path(path)}.tmp.{os.getpid()}"
+    torch.save(state, tmp)
+    os.replace(tmp, optim_path(path))
+
+
+def load_optimizer_state(model, optimizer, path: str, step: int) -> bool:
+    """Restore ``<checkpoint>.optim.pt`` if present (momentum buffers; the fused engine's step counter <- `step`)."""
+    from .parallel.ddp import FusedDDPTrainer
+    from .parallel.flat_ddp import FlatSGD
+    if not os.path.exists(optim_path(path)):
+        return False
+    state = torch.load(optim_path(path), map_location="cpu", weights_only=True)
+    bufs = state["momentum_buffer"]
+    if isinstance(model, FusedDDPTrainer):
+        model.engine.load_optimizer_state({"step": int(step), "momentum_buffer": bufs})
+        if "engine" in state:
+            model.engine.load_step_state(state["engine"])
+        return True
+    if not bufs:
+        return True
+    named = dict(unwrap(model).named_parameters())
+    with torch.no_grad():
+        if isinstance(optimizer, FlatSGD):
+            flat = optimizer.ddp.flat
+            optimizer._buf = torch.zeros_like(flat)
+            if flat.is_cuda:  # the HIP kernel's "buffer not initialised yet" flag: it is now
+                optimizer._first = torch.zeros(1, dtype=torch.int32, device=flat.device)
+            for name, p in named.items():
+                off = (p.data_ptr() - flat.data_ptr()) // flat.element_size()
+                optimizer._buf[off:off + p.numel()].copy_(bufs[name].reshape(-1))
+        else:
+            for name, p in named.items():
+                optimizer.state[p]["momentum_buffer"] = bufs[name].to(p.device, p.dtype).clone()
+    return True
 
 
 def load_dataset(cfg: TrainConfig):
@@ -227,7 +351,8 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
     ckpt = cfg.checkpoint_path or os.path.join(cfg.data_path, CHECKPOINT_NAME)
     fused = isinstance(model, FusedDDPTrainer)
     n_batches = len(train_loader)
-    steps_per_epoch = min(n_batches, cfg.max_steps) if cfg.max_steps else n_batches
+    steps_per_epoch = steps_per_epoch_of(cfg, n_batches)
+    table = lr_table_for(cfg, n_batches)  # None: no optimiser option on, everything below as in the reference
     start_epoch = int(cfg.extra.get("start_epoch", 1))
     global_step = int(cfg.extra.get("start_step", 0))
     history = []
@@ -239,8 +364,25 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
             from .ops.functional import cross_entropy as loss_fn
         if optimizer is None:
             from .parallel.flat_ddp import FlatBucketDDP, FlatSGD
-            optimizer = FlatSGD(model, cfg.lr) if isinstance(model, FlatBucketDDP) else \
-                torch.optim.SGD(model.parameters(), lr=cfg.lr)
+            if table is None:
+                optimizer = FlatSGD(model, cfg.lr) if isinstance(model, FlatBucketDDP) else \
+                    torch.optim.SGD(model.parameters(), lr=cfg.lr)
+            else:
+                optimizer = FlatSGD(model, cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay) \
+                    if isinstance(model, FlatBucketDDP) else \
+                    torch.optim.SGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
+                                    weight_decay=cfg.weight_decay)
+    if table is not None:
+        from .utils.schedule import lr_at
+        if fused and model.engine.cfg.optimizer is None:
+            raise ValueError("optimiser options are on but the fused trainer was built without optimizer= "
+                             "(train.engine_optimizer)")
+        opt_step = int(cfg.extra.get("opt_step", global_step))
+        if cfg.resume:  # momentum buffers of the run being resumed (absent file: they start at zero)
+            load_optimizer_state(model, optimizer, cfg.resume, opt_step)
+        if fused and opt_step != model.engine.optimizer_step():  # the schedule position (no sidecar to restore)
+            model.engine.load_optimizer_state({**model.engine.optimizer_state(), "step": opt_step})
+    last_lr = cfg.lr
     from contextlib import ExitStack
     from .utils.trace import trace_range as record_function  # torch.profiler + roctx ranges
     from .parallel.dist import assert_params_in_sync
@@ -278,6 +420,10 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                     break
                 if cfg.fail_at_step is not None and global_step + nsteps + 1 == cfg.fail_at_step:
                     raise _Fault(f"injected failure at step {cfg.fail_at_step} (rank {rank})")
+                if table is not None:  # this step's learning rate (the fused engine reads the same table on the GPU)
+                    last_lr = lr_at(table, opt_step + nsteps)
+                    for group in optimizer.param_groups:
+                        group["lr"] = last_lr
                 with record_function("forward"), torch.autocast("cuda", torch.bfloat16, enabled=autocast):
                     outputs = model(imgs)
                     loss = loss_fn(outputs.float(), labels)
@@ -289,6 +435,10 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                 loss_sum += loss.item()
                 nsteps += 1
         global_step += nsteps
+        if table is not None:
+            opt_step += nsteps
+            if nsteps:
+                last_lr = lr_at(table, opt_step - 1)
         dt = time.perf_counter() - t0
         if hasattr(model, "check_comm"):  # a peer timeout of the xGMI all-reduce must not go unnoticed
             model.check_comm()            # (rank-divergent gradients): raise before anything is saved
@@ -304,13 +454,18 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                    # exposed wait of the reduction kernel's gradient-segment exchanges, summed per step (xGMI)
                    allreduce_us_per_step=(comm_us / comm_n) if comm_n else None,
                    engine=getattr(eng, "kind_name", cfg.engine if not fused else None),
+                   lr=last_lr,  # the learning rate of the epoch's last step
                    dtype=cfg.dtype, fp32_mode=("3xbf16" if getattr(eng, "kind_name", "") == "sliced" else
                                                "fp32-mfma") if cfg.dtype == "fp32" and fused else None,
                    **ev_rec)
         if should_log(epoch):
             print(epoch_line(epoch, mean), flush=True)
             if cfg.checkpoint:
-                save_checkpoint(model, ckpt, rank, meta={"epoch": epoch, "step": global_step})
+                meta = {"epoch": epoch, "step": global_step}
+                if table is not None:  # optimiser sidecar: momentum buffers + the schedule position
+                    meta["opt_step"] = opt_step
+                    save_optimizer_state(model, optimizer, ckpt, rank, opt_step)
+                save_checkpoint(model, ckpt, rank, meta=meta)
         if ev is not None and rank == 0:
             print(eval_line(epoch, ev.accuracy, ev.mean_loss), flush=True)
         if cfg.check_sync and epoch % cfg.check_sync == 0:
@@ -394,6 +549,8 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
         if meta:
             cfg.extra["start_epoch"] = int(meta.get("epoch", 0)) + 1
             cfg.extra["start_step"] = int(meta.get("step", 0))
+            if "opt_step" in meta:
+                cfg.extra["opt_step"] = int(meta["opt_step"])
     kind = resolve_engine(cfg, device, model)
     if kind == "ops":
         from .ops.models import OpsModel
@@ -403,6 +560,7 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
     if kind == "fused":
         n_idx = len(loader) * loader.batch_size
         return FusedDDPTrainer(model, loader.data, loader.labels, batch_max=loader.batch_size, lr=cfg.lr,
-                               dtype=cfg.dtype, max_indices=max(n_idx, loader.batch_size), comm=cfg.allreduce)
+                               dtype=cfg.dtype, max_indices=max(n_idx, loader.batch_size), comm=cfg.allreduce,
+                               optimizer=engine_optimizer(cfg, len(loader)))
     return FlatBucketDDP(model, bucket_cap_mb=cfg.bucket_mb)
 

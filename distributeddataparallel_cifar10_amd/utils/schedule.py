@@ -1,0 +1,77 @@
+"""Per-step learning-rate tables and the float64 oracle of the engine's optimiser pass (pure Python / numpy).
+
+``lr_table`` returns one learning rate per optimiser step.  The same table drives every engine: the fused engine reads
+it on the device (``csrc/optimizer.hip``: ``lr_table[min(step, n - 1)]``), the ``ops`` and ``torch`` engines set
+``param_groups[...]["lr"]`` from it before each step.
+
+Schedules (``s`` = step index, ``W`` = warm-up steps, ``T`` = total steps, ``t = s - W``):
+
+* warm-up (every kind, ``s < W``): ``base_lr * (s + 1) / (W + 1)`` -- torch ``LambdaLR`` with that factor, i.e. a
+  linear ramp that reaches ``base_lr`` exactly at step ``W``;
+* ``constant``: ``base_lr``;
+* ``step``: ``base_lr * gamma ** (t // step_size)`` -- torch ``StepLR``;
+* ``cosine``: ``min_lr + (base_lr - min_lr) * (1 + cos(pi * t / (T - W))) / 2`` -- torch ``CosineAnnealingLR``
+  (closed form) with ``T_max = T - W``, ``eta_min = min_lr``.
+
+This is torch's ``SequentialLR([LambdaLR, <main>], milestones=[W])``.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+
+KINDS = ("constant", "step", "cosine")
+
+
+def lr_table(kind: str, base_lr: float, total_steps: int, warmup_steps: int = 0, min_lr: float = 0.0,
+             step_size: Optional[int] = None, gamma: float = 0.1) -> np.ndarray:
+    """float64 [total_steps]: the learning rate of every optimiser step."""
+    if kind not in KINDS:
+        raise ValueError(f"lr schedule must be one of {KINDS}, got {kind!r}")
+    total, warm = int(total_steps), int(warmup_steps)
+    if total < 1:
+        raise ValueError("total_steps must be positive")
+    if warm < 0:
+        raise ValueError("warmup_steps must not be negative")
+    if kind == "step" and (step_size is None or int(step_size) < 1):
+        raise ValueError("the step schedule needs step_size >= 1")
+    span = max(total - warm, 1)
+    out = np.empty(total, dtype=np.float64)
+    for s in range(total):
+        if s < warm:
+            out[s] = base_lr * (s + 1) / (warm + 1)
+            continue
+        t = s - warm
+        if kind == "constant":
+            out[s] = base_lr
+        elif kind == "step":
+            out[s] = base_lr * gamma ** (t // int(step_size))
+        else:
+            out[s] = min_lr + (base_lr - min_lr) * (1.0 + math.cos(math.pi * t / span)) / 2.0
+    return out
+
+
+def lr_at(table, step: int) -> float:
+    """The table's value at `step`; past its end the last entry holds (as on the device)."""
+    return float(table[min(max(int(step), 0), len(table) - 1)])
+
+
+def sgd_reference(p, g, buf, lr: float, mu: float, wd: float, inv_ws: float = 1.0):
+    """One update of SGD with momentum and weight decay (dampening 0) in float64 -- the oracle of ``k_apply_opt``:
+
+        d = g * inv_ws + wd * p;  buf' = mu * buf + d;  p' = p - lr * buf'
+
+    `buf` starts at zero, so the first update equals ``d`` (torch initialises its buffer to ``d``: the same).  Takes
+    arrays or tensors; returns ``(p', buf')`` as float64 numpy arrays."""
+    p64, g64, b64 = (_f64(x) for x in (p, g, buf))
+    d = g64 * float(inv_ws) + float(wd) * p64
+    nb = float(mu) * b64 + d
+    return p64 - float(lr) * nb, nb
+
+
+def _f64(x) -> np.ndarray:
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().double().numpy()
+    return np.asarray(x, dtype=np.float64)

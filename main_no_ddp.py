@@ -20,7 +20,7 @@ import torch
 from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader
 from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
 from distributeddataparallel_cifar10_amd.train import TrainConfig, add_cli_args, config_from_args, load_dataset
-from distributeddataparallel_cifar10_amd.train import eval_only, resolve_engine
+from distributeddataparallel_cifar10_amd.train import engine_optimizer, eval_only, resolve_engine
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 
 data_path = '../data/CIFAR-10/'  # reference main_no_ddp.py:17
@@ -51,7 +51,7 @@ def training_loop(model, train_loader):
         # device with fewer CUs, still falls back to the multi-kernel engine with a warning.
         model = FusedDDPTrainer(model, train_loader.data, train_loader.labels, batch_max=train_loader.batch_size,
                                 lr=_cfg.lr, dtype=_cfg.dtype, max_indices=max(n_idx, train_loader.batch_size),
-                                full_device=True)
+                                full_device=True, optimizer=engine_optimizer(_cfg, len(train_loader)))
     elif kind == "ops":  # the ops-layer HIP kernels (flat parameters, packed weights, HIP SGD)
         from distributeddataparallel_cifar10_amd.ops.models import OpsModel
         from distributeddataparallel_cifar10_amd.parallel.flat_ddp import FlatBucketDDP

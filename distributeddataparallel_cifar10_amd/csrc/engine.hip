@@ -70,7 +70,6 @@ struct DcaInit {
   const char* nccl_id;  // 128 bytes (world_size > 1)
   int persistent;       // 1: the one-launch image-sliced persistent step kernel (netresdeep_pks.hip)
   int debug;            // persistent engine: also store X / DY / G / conv1 pre-activations for diagnostics
-  int pk_waves;         // unused (kept for ABI layout; must be 0 or 8)
   int comm_mode;        // world_size > 1: 0 = RCCL inside the step; 1 = external (host drives the all-reduce
                         // between dca_engine_run_part(.., 1) and (.., 2); test/debug path, no RCCL communicator);
                         // 2 = xGMI one-shot (peer-to-peer reads of IPC-mapped gradient slabs, fused with SGD)
@@ -117,10 +116,6 @@ struct Engine {
   int fc_in_step = 1;  // the fc1 / fc-tail gradient segments run on the step kernel's fc workers (pks::N_FCW extra
                        // workgroups beside the backward); off: in the reduction kernel.  Off whenever the step and
                        // its fc workers would exceed the co-resident budget, and when xGMI peers share this device
-  // chunks apply each step's gradient segments in the next step's launch (prologue_ok).  Off by default: same box,
-  // 300 steps bf16, 84.3 / 84.7 us with it against 83.3 / 83.0 us without (profiles/prologue_ab_r5h.log); the
-  // reducers' latency lands on the stem's critical path.  DCA_PKS_PROLOGUE=1 turns it on (bitwise equal: tests).
-  int prologue = 0;
   int shared_device = 0;  // set by the host: number of xGMI ranks on this device (shared-GPU rehearsal; 0/1: not
                           // shared): the coarse 107-segment layout, and fc workers only when every co-scheduled
                           // grid fits (fc_in_step_for), so a spinning kernel always leaves CUs for a peer's step
@@ -189,7 +184,7 @@ static int alloc_workspace(Engine* e) {
       {"COMMT", 16}, {"PKW", PKW_N * 2},
       {"PKS_GRAN", 2 * (size_t)pks::LMAX * pks::GSTR * 8}, {"PKS_YH", 10 * (size_t)pks::LMAX * 2 * 512 * 4},
       {"PKS_BNX", 2 * (size_t)pks::LMAX * 64 * 4},
-      {"PKS_HDONE", (size_t)pks::LMAX * 8 + 256 * 8},  // head-done | prologue ready granules
+      {"PKS_HDONE", (size_t)pks::LMAX * 8},  // head-done granules
       {"C1", e->in.debug ? bmax * 32 * 1024 * 4 : 16},
   };
   size_t total = 0;
@@ -262,15 +257,10 @@ static int set_lds_limits(Engine* e) {
   HIPCK(hipFuncSetAttribute((const void*)e->khead1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->s_head1));
   HIPCK(hipFuncSetAttribute((const void*)e->khead2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->s_head2));
   HIPCK(hipFuncSetAttribute((const void*)e->kbwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dg));
-  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             pks::Plan<0>::TOTAL));
-  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             pks::Plan<1>::TOTAL));
-  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            pks::Plan<0>::TOTAL));
-  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            pks::Plan<1>::TOTAL));
-
   return 0;
 }
 
@@ -354,26 +344,31 @@ static int reduce_grid(const Engine* e, int nred_plus) {
   return e->shared_device > 1 ? std::min(nred_plus, share_budget(e)) : nred_plus;
 }
 
-// Whether a chunk of steps at batch B may apply each step's gradient segments in the NEXT step's launch (the
-// prologue reduction, netresdeep_pks.hip): the SGD must be fused into the segments (world size 1 or xGMI; RCCL and
-// the host all-reduce sit between reduction and SGD), the fc workers run in the step (the prologue leaves the fc
-// segments to them), and the reducers fit beside the live step within the co-residency budget.
-// Off by default (one reduction kernel after every step); DCA_PKS_PROLOGUE=1 turns it on.  With the xGMI exchange the
-// step's ready wait is bounded by the exchange deadline (netresdeep_pks.hip wait_ready), and the form is covered by a
-// two-rank shared-device test (tests/test_ddp_engine_gpu.py::test_xgmi_prologue_two_ranks_one_gpu).
-static bool prologue_ok(const Engine* e, int B) {
-  if (!e->persistent || !e->prologue || e->opt_on) return false;  // (optimiser: the pass sits between the steps)
-  if (e->comm_on && e->in.comm_mode != 2) return false;
-  if (!fc_in_step_for(e, B)) return false;
-  return pks_live(B) + std::max(pks::N_FCW, pks::prologue_segments(seg_ch(e))) <= share_budget(e);
+// The segment arguments of a sliced launch (pks::RedAr): the peers' regions, the exchange's error word and deadline,
+// the segment mode, the flags word and the segment layout.
+static pks::RedAr red_args(const Engine* e, int mode, int flags, unsigned long long deadline) {
+  pks::RedAr ra{};
+  ra.peers = e->peers;
+  ra.err = e->qa.err + 1;
+  ra.deadline = deadline;
+  ra.mode = mode;
+  ra.fc_in_step = flags;
+  ra.seg_ch = seg_ch(e);
+  return ra;
+}
+// Segment mode of a training step: 0 fused SGD (world size 1), 1 gradient only (RCCL / host all-reduce, or the
+// optimiser pass: fc workers included), 2 the xGMI exchange + averaging SGD.
+static int train_mode(const Engine* e) {
+  if (e->opt_on) return 1;
+  if (!e->comm_on) return 0;
+  return e->in.comm_mode == 2 ? 2 : 1;
 }
 
-// The sliced step kernel: step s of its chunk; prev: the previous step's segments are applied in its prologue.
-static int enqueue_pks_step(Engine* e, int B, int s, bool prev) {
+// The sliced step kernel.
+static int enqueue_pks_step(Engine* e, int B) {
   Ctx cx = e->base;
   cx.B = B;
-  const bool multi = e->comm_on, xgmi = multi && e->in.comm_mode == 2;
-  if (xgmi && !e->peers_open) {
+  if (e->comm_on && e->in.comm_mode == 2 && !e->peers_open) {
     g_err = "xGMI all-reduce: peers not mapped (call dca_engine_ipc_open first)";
     return -1;
   }
@@ -382,46 +377,28 @@ static int enqueue_pks_step(Engine* e, int B, int s, bool prev) {
             ") exceed the co-residency budget of " + std::to_string(share_budget(e)) + " per rank";
     return -1;
   }
-  pks::RedAr ra{};
-  ra.peers = e->peers;
-  ra.err = e->qa.err + 1;
-  ra.deadline = e->ar_deadline;
-  ra.mode = e->opt_on ? 1 : (!multi ? 0 : (xgmi ? 2 : 1));  // optimiser: gradient only (fc workers included)
   const bool fc = fc_in_step_for(e, B);
-  ra.fc_in_step = pks::ra_flags(fc, prev, s, 0);
-  ra.seg_ch = seg_ch(e);
-  const int extra = fc ? std::max(pks::N_FCW, prev ? pks::prologue_segments(ra.seg_ch) : 0) : 0;
-  const dim3 grid(pks_grid(B) + extra);
-  // (the prologue form only where this launch applies the previous step's segments)
+  const pks::RedAr ra = red_args(e, train_mode(e), pks::ra_flags(fc, 0, 0), e->ar_deadline);
+  const dim3 grid(pks_grid(B) + (fc ? pks::N_FCW : 0));
   const dim3 blk(pks::NTH);
-  if (e->bf && prev)
-    hipLaunchKernelGGL((pks::k_pks_step<0, true>), grid, blk, pks::Plan<0>::TOTAL, e->st, cx, e->qa, ra);
-  else if (e->bf)
-    hipLaunchKernelGGL((pks::k_pks_step<0, false>), grid, blk, pks::Plan<0>::TOTAL, e->st, cx, e->qa, ra);
-  else if (prev)
-    hipLaunchKernelGGL((pks::k_pks_step<1, true>), grid, blk, pks::Plan<1>::TOTAL, e->st, cx, e->qa, ra);
+  if (e->bf)
+    hipLaunchKernelGGL((pks::k_pks_step<0>), grid, blk, pks::Plan<0>::TOTAL, e->st, cx, e->qa, ra);
   else
-    hipLaunchKernelGGL((pks::k_pks_step<1, false>), grid, blk, pks::Plan<1>::TOTAL, e->st, cx, e->qa, ra);
+    hipLaunchKernelGGL((pks::k_pks_step<1>), grid, blk, pks::Plan<1>::TOTAL, e->st, cx, e->qa, ra);
   HIPCK(hipGetLastError());
   return 0;
 }
 
-// The reduction kernel closing a chunk of `chunk` steps (the last step's segments + its bookkeeping, epoch and
-// cursor advanced by the chunk); then, RCCL / host all-reduce (mode 1), the collective and the averaging SGD.
+// The reduction kernel after a step (its segments + its bookkeeping, epoch and cursor advanced by one step); then,
+// RCCL / host all-reduce (mode 1), the collective and the averaging SGD.
 // part: 0 whole; 1 up to the all-reduce; 2 the SGD after it (comm_mode 1, the host runs the all-reduce between).
-static int enqueue_pks_reduce(Engine* e, int B, int chunk, int part) {
+static int enqueue_pks_reduce(Engine* e, int B, int part) {
   Ctx cx = e->base;
   cx.B = B;
   const bool multi = e->comm_on, xgmi = multi && e->in.comm_mode == 2;
   if (part != 2) {
-    pks::RedAr ra{};
-    ra.peers = e->peers;
-    ra.err = e->qa.err + 1;
-    ra.deadline = e->ar_deadline;
-    ra.mode = e->opt_on ? 1 : (!multi ? 0 : (xgmi ? 2 : 1));
     const bool fc = fc_in_step_for(e, B);
-    ra.fc_in_step = pks::ra_flags(fc, false, 0, chunk);
-    ra.seg_ch = seg_ch(e);
+    const pks::RedAr ra = red_args(e, train_mode(e), pks::ra_flags(fc, 0, 1), e->ar_deadline);
     const dim3 rgrid(reduce_grid(e, pks::reduce_segments(fc, ra.seg_ch) + 1));
     // the lean forms (no fc segments, one exchange mode): world size 1, or the xGMI exchange (also on a shared
     // device, so the multi-rank rehearsals run the form a multi-GPU node runs)
@@ -447,28 +424,14 @@ static int enqueue_pks_reduce(Engine* e, int B, int chunk, int part) {
   return 0;
 }
 
-// One step followed by its own reduction (a chunk of 1): eager runs, the host all-reduce, RCCL.
+// One step followed by its own reduction.
 static int enqueue_step_persistent(Engine* e, int B, int part) {
-  if (part != 2 && enqueue_pks_step(e, B, 0, false)) return -1;
-  return enqueue_pks_reduce(e, B, 1, part);
+  if (part != 2 && enqueue_pks_step(e, B)) return -1;
+  return enqueue_pks_reduce(e, B, part);
 }
 
 // Enqueue one full training step for batch B on e->st (and e->cst for the collectives).
-static int enqueue_step(Engine* e, int B, int part = 0);
-// Enqueue `chunk` consecutive steps: with the prologue reduction `chunk` step kernels and one reduction kernel (one
-// kernel boundary per step), else step + reduction each.
-static int enqueue_chunk(Engine* e, int B, int chunk) {
-  if (!prologue_ok(e, B)) {
-    for (int s = 0; s < chunk; ++s)
-      if (enqueue_step(e, B)) return -1;
-    return 0;
-  }
-  for (int s = 0; s < chunk; ++s)
-    if (enqueue_pks_step(e, B, s, s > 0)) return -1;
-  return enqueue_pks_reduce(e, B, chunk, 0);
-}
-
-static int enqueue_step(Engine* e, int B, int part) {
+static int enqueue_step(Engine* e, int B, int part = 0) {
   if (e->persistent) return enqueue_step_persistent(e, B, part);
   Ctx cx = e->base;
   cx.B = B;
@@ -537,7 +500,7 @@ extern "C" {
 
 const char* dca_last_error() { return g_err.c_str(); }
 
-int dca_abi_version() { return 8; }  // bump with every DcaInit / signature change
+int dca_abi_version() { return 9; }  // bump with every DcaInit / signature change
 
 int dca_nccl_unique_id(char* out128) {
   ncclUniqueId id;
@@ -567,10 +530,6 @@ static int engine_init(Engine* e, const DcaInit* in, int n_indices) {
   }
   e->TPI = 16 / e->R;
   e->persistent = in->persistent != 0;
-  if (in->pk_waves != 0 && in->pk_waves != 8) {
-    g_err = "persistent engine: pk_waves must be 8";
-    return -1;
-  }
   // comm_on: the step ends with a gradient collective + the averaging SGD kernel.  force_comm runs that path at
   // world_size 1 (a 1-rank RCCL communicator) so the graph-captured collective is testable on one GPU; loopback
   // does the same for the xGMI exchange (this rank as its only peer).
@@ -592,10 +551,10 @@ static int engine_init(Engine* e, const DcaInit* in, int n_indices) {
     HIPCK(hipGetDevice(&dev));
     HIPCK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     if (e->bf)
-      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dca::pks::k_pks_step<0, false>, dca::pks::NTH,
+      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dca::pks::k_pks_step<0>, dca::pks::NTH,
                                                         dca::pks::Plan<0>::TOTAL));
     else
-      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dca::pks::k_pks_step<1, false>, dca::pks::NTH,
+      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dca::pks::k_pks_step<1>, dca::pks::NTH,
                                                         dca::pks::Plan<1>::TOTAL));
     // one step workgroup per CU (256 VGPRs): a grid of every CU would leave no slack for anything else on the
     // device (another stream's kernel, another process), so an automatically chosen engine keeps a margin of one
@@ -612,14 +571,6 @@ static int engine_init(Engine* e, const DcaInit* in, int n_indices) {
     }
     e->resident = resident;
     if (const char* fo = getenv("DCA_PKS_FC_IN_STEP")) e->fc_in_step = fo[0] != '0';
-    if (const char* po = getenv("DCA_PKS_PROLOGUE")) e->prologue = po[0] != '0';
-    if (e->prologue) {  // the prologue form is a separate instantiation: it must be as resident as the default one
-      int per_cu_pro = 0;
-      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu_pro, e->bf ? (const void*)dca::pks::k_pks_step<0, true> : (const void*)dca::pks::k_pks_step<1, true>,
-          dca::pks::NTH, e->bf ? dca::pks::Plan<0>::TOTAL : dca::pks::Plan<1>::TOTAL));
-      if (per_cu_pro < per_cu) e->prologue = 0;
-    }
   }
   HIPCK(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
   HIPCK(hipStreamCreateWithFlags(&e->cst, hipStreamNonBlocking));
@@ -799,7 +750,7 @@ int dca_engine_set_epoch(void* h, int device_epoch, int flag_epoch) {
   HIPCK(hipMemcpy(e->qa.epoch, &device_epoch, sizeof(int), hipMemcpyHostToDevice));
   HIPCK(hipMemset(e->qa.gran, 0, 2 * (size_t)dca::pks::LMAX * dca::pks::GSTR * 8));
   HIPCK(hipMemset(e->qa.bnx, 0, 2 * (size_t)dca::pks::LMAX * 64 * 4));
-  HIPCK(hipMemset(e->qa.hdone, 0, (size_t)dca::pks::LMAX * 8 + 256 * 8));
+  HIPCK(hipMemset(e->qa.hdone, 0, (size_t)dca::pks::LMAX * 8));
   if (e->xregion) {
     std::vector<int> f(dca::xg::FLAG_BYTES / 4, flag_epoch);
     HIPCK(hipMemcpy(e->xregion, f.data(), dca::xg::FLAG_BYTES, hipMemcpyHostToDevice));                 // k_xgmi_ar_sgd
@@ -855,7 +806,8 @@ static hipGraphExec_t capture_graph(Engine* e, int B, int chunk) {
     g_err = std::string("hipStreamBeginCapture: ") + hipGetErrorString(ec);
     return nullptr;
   }
-  const int rc = dca::enqueue_chunk(e, B, chunk);
+  int rc = 0;
+  for (int s = 0; s < chunk && !rc; ++s) rc = dca::enqueue_step(e, B);
   ec = hipStreamEndCapture(e->st, &g);
   if (rc) {
     if (ec == hipSuccess) (void)hipGraphDestroy(g);
@@ -1050,17 +1002,11 @@ int dca_engine_ipc_selftest(void* h, const float* src, float* dst, float timeout
   HIPCK(hipMemsetAsync(e->qa.err + 1, 0, sizeof(unsigned), e->st));
   const unsigned long long dl = (unsigned long long)((double)timeout_s * 1e8);
   if (e->persistent) {  // the path a sliced training step uses: per-segment exchange inside the fused reduce kernel
-    dca::pks::RedAr ra{};
-    ra.peers = e->peers;
+    dca::pks::RedAr ra = dca::red_args(e, 3, 0, dl);  // (flags 0: every segment in the reduction kernel)
     ra.peers.ticks = nullptr;
-    ra.err = e->qa.err + 1;
-    ra.deadline = dl;
     ra.st_src = src;
     ra.st_dst = dst;
     ra.st_n = dca::FLAT_N;
-    ra.mode = 3;
-    ra.fc_in_step = 0;  // every segment in the reduction kernel
-    ra.seg_ch = dca::seg_ch(e);
     dca::Ctx cx = e->base;
     cx.B = 1;
     hipLaunchKernelGGL(dca::pks::k_pks_reduce_ar<0>, dim3(dca::reduce_grid(e, dca::pks::seg_layout(ra.seg_ch).nseg)),
@@ -1097,27 +1043,21 @@ int dca_engine_ipc_selftest_fc(void* h, const float* src, float* dst, float time
     return -1;
   }
   HIPCK(hipMemsetAsync(e->qa.err, 0, 2 * sizeof(unsigned), e->st));
-  dca::pks::RedAr ra{};
-  ra.peers = e->peers;
+  dca::pks::RedAr ra = dca::red_args(e, 3, 1, (unsigned long long)((double)timeout_s * 1e8));
   ra.peers.ticks = nullptr;
-  ra.err = e->qa.err + 1;
-  ra.deadline = (unsigned long long)((double)timeout_s * 1e8);
   ra.st_src = src;
   ra.st_dst = dst;
   ra.st_n = dca::FLAT_N;
-  ra.mode = 3;
-  ra.fc_in_step = 1;
-  ra.seg_ch = dca::seg_ch(e);
   dca::Ctx cx = e->base;
   cx.B = 0;  // no step workgroups: the whole grid is fc workers
   // one workgroup per fc segment, or (ranks sharing the device) the rank's CU budget: every rank's workgroup f waits
   // for its peers' workgroup f, so all ranks' grids must be co-resident (a step-kernel workgroup takes a whole CU)
   const dim3 grid(std::min(dca::pks::N_FCW, dca::share_budget(e)));
   if (e->bf)
-    hipLaunchKernelGGL((dca::pks::k_pks_step<0, false>), grid, dim3(dca::pks::NTH), dca::pks::Plan<0>::TOTAL, e->st, cx, e->qa,
+    hipLaunchKernelGGL((dca::pks::k_pks_step<0>), grid, dim3(dca::pks::NTH), dca::pks::Plan<0>::TOTAL, e->st, cx, e->qa,
                        ra);
   else
-    hipLaunchKernelGGL((dca::pks::k_pks_step<1, false>), grid, dim3(dca::pks::NTH), dca::pks::Plan<1>::TOTAL, e->st, cx, e->qa,
+    hipLaunchKernelGGL((dca::pks::k_pks_step<1>), grid, dim3(dca::pks::NTH), dca::pks::Plan<1>::TOTAL, e->st, cx, e->qa,
                        ra);
   HIPCK(hipGetLastError());
   HIPCK(hipStreamSynchronize(e->st));
@@ -1147,16 +1087,11 @@ int dca_engine_ipc_bench(void* h, const float* src, float* dst, int iters, float
   P.ticks = nullptr;  // benchmark traffic stays out of the training comm-time counters
   for (int i = 0; i < iters; ++i) {
     if (e->persistent) {  // the exchange a sliced training step runs: every gradient segment, self-test mode
-      dca::pks::RedAr ra{};
+      dca::pks::RedAr ra = dca::red_args(e, 3, 0, e->ar_deadline);
       ra.peers = P;
-      ra.err = e->qa.err + 1;
-      ra.deadline = e->ar_deadline;
       ra.st_src = src;
       ra.st_dst = dst;
       ra.st_n = dca::FLAT_N;
-      ra.mode = 3;
-      ra.fc_in_step = 0;
-      ra.seg_ch = dca::seg_ch(e);
       dca::Ctx cx = e->base;
       cx.B = 1;
       hipLaunchKernelGGL(dca::pks::k_pks_reduce_ar<0>, dim3(dca::reduce_grid(e, dca::pks::seg_layout(ra.seg_ch).nseg)),
@@ -1329,8 +1264,6 @@ int dca_engine_fc_in_step(void* h, int B) {
   return e->persistent && fc_in_step_for(e, B) ? 1 : 0;
 }
 
-// Whether graph chunks at batch B apply each step's gradient segments in the next step's launch (prologue_ok).
-int dca_engine_prologue(void* h, int B) { return dca::prologue_ok((Engine*)h, B) ? 1 : 0; }
 
 // Handle of the engine stream (so Python can order torch work against it).
 void* dca_engine_stream(void* h) { return ((Engine*)h)->st; }

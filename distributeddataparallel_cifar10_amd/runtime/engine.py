@@ -65,7 +65,6 @@ class _DcaInit(ctypes.Structure):
         ("nccl_id", ctypes.c_char_p),
         ("persistent", ctypes.c_int),
         ("debug", ctypes.c_int),
-        ("pk_waves", ctypes.c_int),
         ("comm_mode", ctypes.c_int),
         ("force_comm", ctypes.c_int),
         ("auto_engine", ctypes.c_int),
@@ -146,7 +145,6 @@ class EngineConfig:
     rows: int = 4                # multi-kernel engine: trunk rows per workgroup tile (2 or 4)
     persistent: Optional[bool] = None  # one-launch persistent step kernel (default: on; image-sliced)
     debug: bool = False          # persistent engine: also store per-block dy / residual grads (diagnostics)
-    pk_waves: int = 8            # (ABI field; the sliced kernel always runs 8 waves per workgroup)
     world_size: int = 1
     rank: int = 0
     comm: str = "rccl"           # world_size > 1: "rccl" (all-reduce inside the graph-captured step),
@@ -210,7 +208,7 @@ class NetResDeepEngine:
             bmax=int(cfg.batch_max), bf16=1 if cfg.dtype == "bf16" else 0, rows=int(cfg.rows), lr=float(cfg.lr),
             bn_mom=float(cfg.bn_momentum), bn_eps=float(cfg.bn_eps), world_size=int(cfg.world_size),
             rank=int(cfg.rank), nccl_id=ctypes.cast(self._nccl_id, ctypes.c_char_p),
-            persistent=1 if cfg.persistent else 0, debug=1 if cfg.debug else 0, pk_waves=int(cfg.pk_waves),
+            persistent=1 if cfg.persistent else 0, debug=1 if cfg.debug else 0,
             comm_mode={"rccl": 0, "external": 1, "xgmi": 2}[cfg.comm], force_comm=1 if cfg.force_comm else 0,
             # the automatic choice keeps one CU of co-residency slack (batch 64 -> multi-kernel engine) unless the
             # caller owns the device (cfg.full_device, or DCA_PKS_ALLOW_FULL_DEVICE=1): then all 256 CUs
@@ -355,11 +353,6 @@ class NetResDeepEngine:
     def fc_in_step(self, batch: int) -> bool:
         """Whether a step at this batch size runs the fc gradient segments on the step kernel's fc workers."""
         return bool(self.lib.dca_engine_fc_in_step(self.h, int(batch)))
-
-    def prologue(self, batch: int) -> bool:
-        """Whether graph chunks at this batch size reduce each step's gradient segments in the next step's launch
-        (DCA_PKS_PROLOGUE=1, where the budget and the all-reduce allow it)."""
-        return bool(self.lib.dca_engine_prologue(self.h, int(batch)))
 
     # ---- state sync ---------------------------------------------------------------------------------------
     def derive(self):

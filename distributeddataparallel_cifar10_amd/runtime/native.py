@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported before the native library, see mod
 
 from .. import build as _build
 
-ABI_VERSION = 8  # csrc/engine.hip dca_abi_version(): DcaInit layout / C signatures
+ABI_VERSION = 9  # csrc/engine.hip dca_abi_version(): DcaInit layout / C signatures
 _lock = threading.Lock()
 _lib = None
 
@@ -59,7 +59,6 @@ def _declare(lib):
     lib.dca_engine_set_epoch.argtypes = [c_void_p, c_int, c_int]
     lib.dca_engine_epoch.argtypes = [c_void_p, ctypes.POINTER(c_int)]
     lib.dca_engine_fc_in_step.argtypes = [c_void_p, c_int]
-    lib.dca_engine_prologue.argtypes = [c_void_p, c_int]
     lib.dca_engine_set_optimizer.argtypes = [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float]
     lib.dca_engine_set_lr_table.argtypes = [c_void_p, c_void_p, c_int]
     lib.dca_engine_opt_step.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]

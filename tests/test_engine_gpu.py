@@ -169,11 +169,10 @@ def test_learnable_epochs_track_pytorch(gpu, dtype, tol):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
-def test_prologue_reduction_bitwise(gpu, dtype, monkeypatch):
-    """Graph chunks with the prologue reduction (each step's gradient segments applied at the start of the next step's
-    launch, one reduction kernel per chunk) train bitwise like one reduction kernel after every step
-    (DCA_PKS_PROLOGUE=0): 37 steps = chunks of 16 + 16 + 4 + 1, a ragged batch in between, then the epoch / cursor
-    bases and the loss accumulator agree too."""
+def test_graph_chunks_match_eager_bitwise(gpu, dtype):
+    """Replayed graph chunks train bitwise like the same steps enqueued eagerly (the same kernels in the same order,
+    every sum in a fixed order): 37 steps = chunks of 16 + 16 + 4 and a ragged batch of 20, then the epoch / cursor
+    bases and the loss accumulator agree too, and neither engine reports an exchange error."""
     import copy
     from distributeddataparallel_cifar10_amd.data.synthetic import synthetic_cifar
     from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
@@ -182,16 +181,15 @@ def test_prologue_reduction_bitwise(gpu, dtype, monkeypatch):
     torch.manual_seed(9)
     m0 = NetResDeep()
     out = []
-    for pro in ("1", "0"):
-        monkeypatch.setenv("DCA_PKS_PROLOGUE", pro)
+    for graph in (True, False):
         m = copy.deepcopy(m0).to(gpu)
         eng = NetResDeepEngine(m, data.to(gpu), labels.to(gpu), EngineConfig(batch_max=32, dtype=dtype))
-        assert eng.prologue(32) == (pro == "1")  # the prologue form really runs (as resident as the default form)
         eng.set_indices(list(range(2048)))
         eng.set_cursor(0)
         eng.read_loss(reset=True)
-        eng.run(32, 36)
-        eng.run(20, 1)
+        eng.run(32, 36, graph=graph)
+        eng.run(20, 1, graph=graph)
+        eng.check_errors()
         loss, steps = eng.read_loss()
         out.append((loss, steps, eng.epoch(), torch.cat([p.detach().reshape(-1).cpu() for p in m.parameters()]),
                     m.resblocks[0].batch_norm.running_var.detach().cpu().clone(),

@@ -5,7 +5,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <tuple>
 #include <cstring>
 #include <string>
 #include <cstdlib>
@@ -59,31 +58,66 @@ int cu_count(int* ncu) {
   }
   return 0;
 }
-inline int nparts_rows(long M) { return (int)((M + dca::ops::BN_ROWS - 1) / dca::ops::BN_ROWS); }
-// BN kernels: 16 channel lanes (256 contiguous bytes per row and wave instruction) when C % 128 == 0, else 8
 // finalize threads per workgroup: 1024 when one workgroup reduces one channel's partial rows (C < 256)
 #define BN_FIN_NTH(CW) ((CW) == 1 ? 1024 : 256)
 
-// Per-shape policy of the large BN passes (bench/micro/bn_micro.hip, profiles/bn_micro_r4s.log; same box, ResNet-50
-// batch-256 shapes): tensors of >= 2^26 elements stream with non-temporal loads / stores (statistics 181.6 -> 145.5 us,
-// residual apply 251.6 -> 209.5 us at 802816 x 256); the 16-lane backward apply of >= 2^25 elements also takes 128
-// rows per workgroup (twice the workgroups: 104.5 -> 84.2 us at 50176 x 1024).  Smaller tensors keep the default
-// cache policy and 256 rows (they are re-read while still in the Infinity Cache).  Same box, whole step: 10,292 ->
+// Per-shape policy of the BN passes, all of it in bn_plan below: a pure function of the shape and the fused form (no
+// HIP call, no environment), exported as dca_ops_bn_plan and tested against a hand-written table on the CPU
+// (tests/test_native_build.py); every launcher below takes its kernel and grid from the plan.
+//   lanes          16 channel lanes (256 contiguous bytes per row and wave instruction) when C % 128 == 0, else 8
+//   forward apply  tensors of >= 2^26 elements (16 lanes) stream with non-temporal loads / stores and take 128 rows
+//                  per workgroup; every other tensor the default cache policy and BN_ROWS = 256 rows
+//   backward stats non-temporal under the same rule; always BN_ROWS rows (one partial row per workgroup)
+//   backward apply 16 lanes and >= 2^25 elements: 128 rows per workgroup (twice the workgroups) and non-temporal;
+//                  else 256 rows and the default policy
+//   bwd_mode       how dz is recovered: the stored mask when there is one, else recomputed (BWD_RES for
+//                  ReLU(bn + r), BWD_RELU for the other ReLU forms), BWD_PLAIN without ReLU; -1 where
+//                  dca_ops_bn_bwd rejects the form (a join without ReLU, a mask on any other form than
+//                  ReLU(bn + r) or the plain BN that feeds one)
+//   raff           the residual's own BN applied on the fly (BnRes), res_mode 2 only
+// Measured on bench/micro/bn_micro.hip (profiles/bn_micro_r4s.log; same box, ResNet-50 batch-256 shapes): NT
+// statistics 181.6 -> 145.5 us, residual apply 251.6 -> 209.5 us at 802816 x 256; backward apply 104.5 -> 84.2 us
+// at 50176 x 1024.  Smaller tensors are re-read while still in the Infinity Cache.  Same box, whole step: 10,292 ->
 // 10,494 img/s (profiles/resnet50_bntune_ab_r4t.log).
 using namespace dca::ops;
-inline bool bn_nt(long M, int C) { return C % 128 == 0 && (long)M * C >= (1L << 26); }
-inline bool bn_bwd_apply_fine(long M, int C) { return C % 128 == 0 && (long)M * C >= (1L << 25); }
-inline int bn_bwd_mode(int relu, int res_mode, const void* mask) {
-  if (mask) return BWD_MASK;
-  if (relu) return res_mode == 2 ? BWD_RES : BWD_RELU;
-  return BWD_PLAIN;
+struct BnPlan {  // must match ops/_native.py::BnPlan
+  int lanes;                       // 8 | 16
+  int apply_rows, apply_nt, raff;  // k_bn_apply<lanes, apply_rows, apply_nt, raff>
+  int bwd_mode;                    // BWD_PLAIN..BWD_MASK, -1: no backward for this form
+  int bwd_stats_nt;                // k_bn_bwd_stats<lanes, bwd_mode, bwd_stats_nt>
+  int bwd_rows, bwd_apply_nt;      // k_bn_bwd_apply<lanes, bwd_mode, bwd_rows, bwd_apply_nt>
+};
+// nullptr and *out, or the reason the shape is rejected
+inline const char* bn_plan(long M, int C, int relu, int res_mode, int has_mask, int raff, BnPlan* out) {
+  if (M < 1 || C < 8 || C % 8 != 0) return "bn: M >= 1 rows of C channels, C a multiple of 8";
+  if (res_mode < 0 || res_mode > 2) return "bn: res_mode is 0, 1 or 2";
+  if (raff && res_mode != 2) return "bn: an on-the-fly residual BN needs res_mode 2";
+  const bool wide = C % 128 == 0;
+  const bool nt = wide && M * C >= (1L << 26), fine = wide && M * C >= (1L << 25);
+  BnPlan p;
+  p.lanes = wide ? 16 : 8;
+  p.apply_rows = nt ? 128 : BN_ROWS;
+  p.apply_nt = nt;
+  p.raff = raff != 0;
+  if (res_mode == 2 && !relu) p.bwd_mode = -1;
+  else if (has_mask) p.bwd_mode = (relu && res_mode == 2) || (!relu && res_mode == 0) ? BWD_MASK : -1;
+  else if (relu) p.bwd_mode = res_mode == 2 ? BWD_RES : BWD_RELU;
+  else p.bwd_mode = BWD_PLAIN;
+  p.bwd_stats_nt = nt;
+  p.bwd_rows = fine ? 128 : BN_ROWS;
+  p.bwd_apply_nt = fine;
+  *out = p;
+  return nullptr;
+}
+inline dim3 bn_grid(const BnPlan& p, long M, int C, int rows) {
+  return dim3((unsigned)((C + 8 * p.lanes - 1) / (8 * p.lanes)), (unsigned)((M + rows - 1) / rows));
 }
 template <int CL, typename... A>
-void bn_stats_launch(int mode, bool nt, dim3 g, hipStream_t st, A... a) {
-#define BST(MO)                                                                                  \
-  if (nt) hipLaunchKernelGGL((k_bn_bwd_stats<CL, MO, true>), g, dim3(256), 0, st, a...);         \
+void bn_stats_launch_t(const BnPlan& p, dim3 g, hipStream_t st, A... a) {
+#define BST(MO)                                                                                          \
+  if (p.bwd_stats_nt) hipLaunchKernelGGL((k_bn_bwd_stats<CL, MO, true>), g, dim3(256), 0, st, a...);     \
   else hipLaunchKernelGGL((k_bn_bwd_stats<CL, MO, false>), g, dim3(256), 0, st, a...)
-  switch (mode) {
+  switch (p.bwd_mode) {
     case BWD_PLAIN: BST(BWD_PLAIN); break;
     case BWD_RELU: BST(BWD_RELU); break;
     case BWD_RES: BST(BWD_RES); break;
@@ -91,14 +125,18 @@ void bn_stats_launch(int mode, bool nt, dim3 g, hipStream_t st, A... a) {
   }
 #undef BST
 }
+template <typename... A>
+void bn_stats_launch(const BnPlan& p, long M, int C, hipStream_t st, A... a) {
+  const dim3 g = bn_grid(p, M, C, BN_ROWS);
+  if (p.lanes == 16) bn_stats_launch_t<16>(p, g, st, a...);
+  else bn_stats_launch_t<8>(p, g, st, a...);
+}
 template <int CL, typename... A>
-void bn_bwd_apply_launch(int mode, bool fine, long M, int C, hipStream_t st, A... a) {
-  const unsigned gx = (unsigned)((C + 8 * CL - 1) / (8 * CL));
-  const dim3 g128(gx, (unsigned)((M + 127) / 128)), g256(gx, (unsigned)((M + 255) / 256));
-#define BAP(MO)                                                                                          \
-  if (fine) hipLaunchKernelGGL((k_bn_bwd_apply<CL, MO, 128, true>), g128, dim3(256), 0, st, a...);      \
-  else hipLaunchKernelGGL((k_bn_bwd_apply<CL, MO, 256, false>), g256, dim3(256), 0, st, a...)
-  switch (mode) {
+void bn_bwd_apply_launch_t(const BnPlan& p, dim3 g, hipStream_t st, A... a) {
+#define BAP(MO)                                                                                                \
+  if (p.bwd_rows == 128) hipLaunchKernelGGL((k_bn_bwd_apply<CL, MO, 128, true>), g, dim3(256), 0, st, a...);   \
+  else hipLaunchKernelGGL((k_bn_bwd_apply<CL, MO, BN_ROWS, false>), g, dim3(256), 0, st, a...)
+  switch (p.bwd_mode) {
     case BWD_PLAIN: BAP(BWD_PLAIN); break;
     case BWD_RELU: BAP(BWD_RELU); break;
     case BWD_RES: BAP(BWD_RES); break;
@@ -106,23 +144,24 @@ void bn_bwd_apply_launch(int mode, bool fine, long M, int C, hipStream_t st, A..
   }
 #undef BAP
 }
-template <bool RAFF, typename... A>
-void bn_apply_launch_t(long M, int C, hipStream_t st, A... a) {
-  if (C % 128 != 0) {
-    hipLaunchKernelGGL((k_bn_apply<8, BN_ROWS, false, RAFF>), dim3((C + 63) / 64, nparts_rows(M)), dim3(256), 0, st, a...);
-  } else if (bn_nt(M, C)) {
-    hipLaunchKernelGGL((k_bn_apply<16, 128, true, RAFF>), dim3(C / 128, (unsigned)((M + 127) / 128)), dim3(256), 0, st,
-                       a...);
-  } else {
-    hipLaunchKernelGGL((k_bn_apply<16, BN_ROWS, false, RAFF>), dim3(C / 128, nparts_rows(M)), dim3(256), 0, st, a...);
-  }
-}
-// (the residual's on-the-fly BN -- the last argument, BnRes -- selects its own instantiation)
 template <typename... A>
-void bn_apply_launch(long M, int C, hipStream_t st, A... a) {
-  const BnRes rb = std::get<sizeof...(A) - 1>(std::tuple<A...>(a...));
-  if (rb.stats) bn_apply_launch_t<true>(M, C, st, a...);
-  else bn_apply_launch_t<false>(M, C, st, a...);
+void bn_bwd_apply_launch(const BnPlan& p, long M, int C, hipStream_t st, A... a) {
+  const dim3 g = bn_grid(p, M, C, p.bwd_rows);
+  if (p.lanes == 16) bn_bwd_apply_launch_t<16>(p, g, st, a...);
+  else bn_bwd_apply_launch_t<8>(p, g, st, a...);
+}
+template <bool RAFF, typename... A>
+void bn_apply_launch_t(const BnPlan& p, dim3 g, hipStream_t st, A... a) {
+  if (p.lanes == 8) hipLaunchKernelGGL((k_bn_apply<8, BN_ROWS, false, RAFF>), g, dim3(256), 0, st, a...);
+  else if (p.apply_nt) hipLaunchKernelGGL((k_bn_apply<16, 128, true, RAFF>), g, dim3(256), 0, st, a...);
+  else hipLaunchKernelGGL((k_bn_apply<16, BN_ROWS, false, RAFF>), g, dim3(256), 0, st, a...);
+}
+// (the residual's on-the-fly BN -- the last argument, BnRes, the plan's raff -- selects its own instantiation)
+template <typename... A>
+void bn_apply_launch(const BnPlan& p, long M, int C, hipStream_t st, A... a) {
+  const dim3 g = bn_grid(p, M, C, p.apply_rows);
+  if (p.raff) bn_apply_launch_t<true>(p, g, st, a...);
+  else bn_apply_launch_t<false>(p, g, st, a...);
 }
 // BN partial-row reduction (MODE 0 forward statistics, MODE 1 backward sums): with ticket words (ceil(C / 64), zero)
 // the coalesced ticketed kernel (k_bn_fin_ticket; the partial rows are overwritten), else the per-channel one
@@ -161,7 +200,16 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 14; }
+int dca_ops_abi_version() { return 15; }
+
+// The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
+// of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
+// with the error set for a shape it rejects.  Must match ops/_native.py::BnPlan.
+int dca_ops_bn_plan(long M, int C, int relu, int res_mode, int has_mask, int raff, BnPlan* out) {
+  const char* e = bn_plan(M, C, relu, res_mode, has_mask, raff, out);
+  REQUIRE(!e, e);
+  return 0;
+}
 
 // The rule alone, callable with no device: the route dca_ops_gemm would take on a device of ncu compute units under
 // DCA_OPS_STREAM = stream_mode; -1 with the error set for a shape it rejects.  Must match ops/_native.py::GemmRoute.
@@ -242,14 +290,16 @@ int dca_ops_col2im(const void* dcols, void* dx, const ConvGeom* geom, int accumu
 int dca_ops_bn_fwd(const void* x, const void* r, void* out, float* part, float* stats, const float* gamma,
                    const float* beta, float* rm, float* rv, long M, int C, float eps, float momentum, int relu,
                    int res_mode, unsigned* ticket, void* stream) {
-  REQUIRE(C % 8 == 0, "bn: C must be a multiple of 8");
+  BnPlan p;
+  const char* e = bn_plan(M, C, relu, res_mode, 0, 0, &p);
+  REQUIRE(!e, e);
   REQUIRE(res_mode == 0 || r != nullptr, "bn: residual missing");
   hipStream_t st = (hipStream_t)stream;
   const int nparts = (int)((M + BN_ROWS - 1) / BN_ROWS);
   hipLaunchKernelGGL(k_bn_stats, dim3((C + 63) / 64, nparts), dim3(256), 0, st, (const bf16_t*)x, rm, (float2*)part,
                      (int)M, C);
   bn_fin_launch<0>(part, nparts, M, C, rm, rv, stats, eps, momentum, 0, ticket, st);
-  bn_apply_launch(M, C, st, (const bf16_t*)x, (const bf16_t*)r,
+  bn_apply_launch(p, M, C, st, (const bf16_t*)x, (const bf16_t*)r,
                      (bf16_t*)out, (const float2*)stats, gamma, beta, M, C, relu, res_mode, (uint8_t*)nullptr,
                      (const float*)nullptr, (unsigned*)nullptr, (uint8_t*)nullptr, BnRes{});
   OPCK(hipGetLastError());
@@ -268,17 +318,19 @@ int dca_ops_bn_fwd_parts(const void* x, const void* r, void* out, float* part, i
                          float momentum, int relu, int res_mode, void* q, const float* amax_prev, unsigned* amax_out,
                          void* mask, const float* rstats, const float* rgamma, const float* rbeta, unsigned* ticket,
                          void* stream) {
-  REQUIRE(C % 8 == 0, "bn: C must be a multiple of 8");
+  REQUIRE(!rstats || (res_mode == 2 && rgamma && rbeta), "bn: an on-the-fly residual BN needs res_mode 2");
+  BnPlan p;
+  const char* e = bn_plan(M, C, relu, res_mode, mask != nullptr, rstats != nullptr, &p);
+  REQUIRE(!e, e);
   REQUIRE(res_mode == 0 || r != nullptr, "bn: residual missing");
   REQUIRE(!q || (amax_prev && amax_out), "bn: fp8 output needs amax_prev and amax_out");
   REQUIRE(!mask || (relu && res_mode == 2), "bn: the stored mask is for ReLU(bn + r)");
   hipStream_t st = (hipStream_t)stream;
-  REQUIRE(!rstats || (res_mode == 2 && rgamma && rbeta), "bn: an on-the-fly residual BN needs res_mode 2");
   REQUIRE(out || (!q && !mask), "bn: statistics only: no fp8 copy / mask");
   if (q) OPCK(hipMemsetAsync(amax_out, 0, sizeof(unsigned), st));
   bn_fin_launch<0>(part, nparts, M, C, rm, rv, stats, eps, momentum, 0, ticket, st);
   if (out)
-    bn_apply_launch(M, C, st, (const bf16_t*)x, (const bf16_t*)r,
+    bn_apply_launch(p, M, C, st, (const bf16_t*)x, (const bf16_t*)r,
                     (bf16_t*)out, (const float2*)stats, gamma, beta, M, C, relu, res_mode, (uint8_t*)q, amax_prev,
                     amax_out, (uint8_t*)mask, BnRes{(const float2*)rstats, rgamma, rbeta});
   OPCK(hipGetLastError());
@@ -289,11 +341,13 @@ int dca_ops_bn_fwd_parts(const void* x, const void* r, void* out, float* part, i
 // stats: [C] float2 scratch (mean, invstd).  No running-stat update.
 int dca_ops_bn_eval(const void* x, const void* r, void* out, float* stats, const float* gamma, const float* beta,
                     const float* rm, const float* rv, long M, int C, float eps, int relu, int res_mode, void* stream) {
-  REQUIRE(C % 8 == 0, "bn: C must be a multiple of 8");
+  BnPlan p;
+  const char* e = bn_plan(M, C, relu, res_mode, 0, 0, &p);
+  REQUIRE(!e, e);
   REQUIRE(res_mode == 0 || r != nullptr, "bn: residual missing");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_bn_eval_stats, dim3((C + 255) / 256), dim3(256), 0, st, rm, rv, (float2*)stats, C, eps);
-  bn_apply_launch(M, C, st, (const bf16_t*)x, (const bf16_t*)r,
+  bn_apply_launch(p, M, C, st, (const bf16_t*)x, (const bf16_t*)r,
                      (bf16_t*)out, (const float2*)stats, gamma, beta, M, C, relu, res_mode, (uint8_t*)nullptr,
                      (const float*)nullptr, (unsigned*)nullptr, (uint8_t*)nullptr, BnRes{});
   OPCK(hipGetLastError());
@@ -305,33 +359,23 @@ int dca_ops_bn_bwd(const void* dy, const void* x, const void* r, const float* st
                    const float* beta, float* part, float* sums, float* dgamma, float* dbeta, void* dx, void* dr,
                    long M, int C, int relu, int res_mode, int accumulate, const void* mask, unsigned* ticket,
                    void* stream) {
-  REQUIRE(C % 8 == 0, "bn: C must be a multiple of 8");
+  BnPlan p;
+  const char* e = bn_plan(M, C, relu, res_mode, mask != nullptr, 0, &p);
+  REQUIRE(!e, e);
   // dr (= dz) may be omitted with the mask: the residual's consumer then reads dy and the mask itself
   REQUIRE(res_mode != 2 || mask != nullptr || (r != nullptr && dr != nullptr), "bn bwd: residual tensors missing");
   // mask: ReLU(bn + r)'s own stored mask (relu, res_mode 2), or -- a plain BN whose output is that r (ResNet
   // downsample branch: no relu, res_mode 0) -- the consumer's mask applied to the consumer's dout, passed as dy
   REQUIRE(!mask || (relu && res_mode == 2) || (!relu && res_mode == 0), "bn bwd: unsupported mask use");
   REQUIRE(res_mode != 2 || relu, "bn bwd: a residual join without ReLU is not supported");
+  REQUIRE(p.bwd_mode >= 0, "bn bwd: unsupported form");
   hipStream_t st = (hipStream_t)stream;
   const int nparts = (int)((M + BN_ROWS - 1) / BN_ROWS);
-  const int mode = bn_bwd_mode(relu, res_mode, mask);
-  if (C % 128 == 0)
-    bn_stats_launch<16>(mode, bn_nt(M, C), dim3(C / 128, nparts), st, (const bf16_t*)dy, (const bf16_t*)x,
-                        (const bf16_t*)r, (const float2*)stats, gamma, beta, (float2*)part, (int)M, C,
-                        (const uint8_t*)mask);
-  else
-    bn_stats_launch<8>(mode, false, dim3((C + 63) / 64, nparts), st, (const bf16_t*)dy, (const bf16_t*)x,
-                       (const bf16_t*)r, (const float2*)stats, gamma, beta, (float2*)part, (int)M, C,
-                       (const uint8_t*)mask);
+  bn_stats_launch(p, M, C, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)r, (const float2*)stats, gamma,
+                  beta, (float2*)part, (int)M, C, (const uint8_t*)mask);
   bn_fin_launch<1>(part, nparts, M, C, dgamma, dbeta, sums, 0.f, 0.f, accumulate, ticket, st);
-  if (C % 128 == 0)
-    bn_bwd_apply_launch<16>(mode, bn_bwd_apply_fine(M, C), M, C, st, (const bf16_t*)dy, (const bf16_t*)x,
-                            (const bf16_t*)r, (const float2*)stats, gamma, beta, (const float2*)sums, (bf16_t*)dx,
-                            (bf16_t*)dr, M, C, (const uint8_t*)mask);
-  else
-    bn_bwd_apply_launch<8>(mode, false, M, C, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)r,
-                           (const float2*)stats, gamma, beta, (const float2*)sums, (bf16_t*)dx, (bf16_t*)dr, M, C,
-                           (const uint8_t*)mask);
+  bn_bwd_apply_launch(p, M, C, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)r, (const float2*)stats,
+                      gamma, beta, (const float2*)sums, (bf16_t*)dx, (bf16_t*)dr, M, C, (const uint8_t*)mask);
   OPCK(hipGetLastError());
   return 0;
 }

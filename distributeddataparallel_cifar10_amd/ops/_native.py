@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 _lock = threading.Lock()
 _lib = None
 
@@ -44,6 +44,17 @@ class GemmRoute(ctypes.Structure):
                 ("masked_copy", c_int), ("reduce", c_int)]
 
 
+class BnPlan(ctypes.Structure):
+    """Mirror of csrc/ops_api.hip::BnPlan: the kernel instantiations the BN entry points launch for a shape and form
+    (k_bn_apply<lanes, apply_rows, apply_nt, raff>, k_bn_bwd_stats<lanes, bwd_mode, bwd_stats_nt>,
+    k_bn_bwd_apply<lanes, bwd_mode, bwd_rows, bwd_apply_nt>; bwd_mode -1: the form has no backward)."""
+    _fields_ = [(n, c_int) for n in ("lanes", "apply_rows", "apply_nt", "raff", "bwd_mode", "bwd_stats_nt",
+                                     "bwd_rows", "bwd_apply_nt")]
+
+
+BWD_PLAIN, BWD_RELU, BWD_RES, BWD_MASK = range(4)  # csrc/ops_nn.hip
+
+
 class ConvGeom(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "H", "W", "C", "KH", "KW", "stride", "pad", "Ho", "Wo", "K", "Kp")]
 
@@ -70,6 +81,7 @@ def _declare(lib):
     lib.dca_ops_gemm.argtypes = [P(GemmArgs), c_void_p]
     lib.dca_ops_gemm_route.argtypes = [P(GemmArgs), c_int, c_int, P(GemmRoute)]
     lib.dca_ops_gemm_last_route.argtypes = [P(GemmRoute)]
+    lib.dca_ops_bn_plan.argtypes = [c_long, c_int, c_int, c_int, c_int, c_int, P(BnPlan)]
     lib.dca_ops_im2col.argtypes = [c_void_p, c_void_p, P(ConvGeom), c_void_p]
     lib.dca_ops_col2im.argtypes = [c_void_p, c_void_p, P(ConvGeom), c_int, c_void_p]
     lib.dca_ops_bn_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -150,6 +162,14 @@ def last_gemm_kernel() -> str:
     r = GemmRoute()
     check(lib().dca_ops_gemm_last_route(ctypes.byref(r)), "gemm_last_route")
     return r.name.decode()
+
+
+def bn_plan(M: int, C: int, relu, res_mode: int, has_mask=False, raff=False) -> BnPlan:
+    """The kernels the BN entry points launch for M rows of C channels in this fused form (no device needed)."""
+    p = BnPlan()
+    check(lib().dca_ops_bn_plan(M, C, int(bool(relu)), int(res_mode), int(bool(has_mask)), int(bool(raff)),
+                                ctypes.byref(p)), "bn_plan")
+    return p
 
 
 def ptr(t):

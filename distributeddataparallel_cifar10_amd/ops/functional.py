@@ -762,6 +762,24 @@ class _Conv2d(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+def _bn_fwd_parts(y, r, out, part, nparts, stats, gamma, beta, running_mean, running_var, eps, momentum, relu,
+                  res_mode, q=None, amax_prev=None, amax_out=None, mask=None, lazy_res=None) -> None:
+    """The fused BN forward from partial sums (dca_ops_bn_fwd_parts): finalises the ``nparts`` rows of ``part``
+    ([nparts, C, 2] fp32 sums of y - running_mean and its square, overwritten) into ``stats`` and the running buffers,
+    then writes ``out`` = the fused form of y [.., C] bf16 and the residual r (None: statistics only).  q / amax_prev /
+    amax_out: the optional fp8 copy with delayed scaling; mask: [M C / 8] bytes for the ReLU bits (relu, res_mode 2);
+    lazy_res: (stats, gamma, beta) of the training BN whose raw input r is, applied on the fly."""
+    C = y.shape[-1]
+    M = y.numel() // C
+    N.check(N.lib().dca_ops_bn_fwd_parts(N.ptr(y), N.ptr(r), N.ptr(out), N.ptr(part), nparts, N.ptr(stats),
+                                         N.ptr(gamma), N.ptr(beta), N.ptr(running_mean), N.ptr(running_var), M, C,
+                                         float(eps), float(momentum), int(relu), int(res_mode), N.ptr(q),
+                                         N.ptr(amax_prev), N.ptr(amax_out), N.ptr(mask),
+                                         *((N.ptr(t) for t in lazy_res) if lazy_res is not None else (None,) * 3),
+                                         N.ptr(_ticket(y.device, (C + 63) // 64)), N.stream(y.device)),
+            "bn_fwd_parts")
+
+
 class _ConvBNAct(torch.autograd.Function):
     """conv (no bias) -> BatchNorm (train) -> ReLU / residual, with the BN statistics computed in the conv
     GEMM's epilogue (no separate statistics pass over the conv output)."""
@@ -814,14 +832,10 @@ class _ConvBNAct(torch.autograd.Function):
             q = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
         # ReLU(bn + r): the forward stores the ReLU mask as bits, so the backward reads M*C/8 bytes instead of r
         mask = torch.empty(M * co // 8, dtype=torch.uint8, device=x.device) if relu and res_mode == 2 else None
-        N.check(N.lib().dca_ops_bn_fwd_parts(N.ptr(y), N.ptr(r), N.ptr(out), N.ptr(part), nparts, N.ptr(stats),
-                                             N.ptr(gamma), N.ptr(beta), N.ptr(running_mean), N.ptr(running_var), M, co,
-                                             float(eps), float(momentum), int(relu), int(res_mode), N.ptr(q),
-                                             N.ptr(emit.amax_prev) if q is not None else None,
-                                             N.ptr(emit.amax_out) if q is not None else None, N.ptr(mask),
-                                             *((N.ptr(t) for t in rl[1:]) if rl is not None else (None,) * 3),
-                                             N.ptr(_ticket(x.device, (co + 63) // 64)), N.stream(x.device)),
-                "bn_fwd_parts")
+        _bn_fwd_parts(y, r, out, part, nparts, stats, gamma, beta, running_mean, running_var, eps, momentum, relu,
+                      res_mode, q=q, amax_prev=emit.amax_prev if q is not None else None,
+                      amax_out=emit.amax_out if q is not None else None, mask=mask,
+                      lazy_res=rl[1:] if rl is not None else None)
         if q is not None:
             emit.q, emit.src_ptr = q, out.data_ptr()
         if rl is not None:

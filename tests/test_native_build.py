@@ -196,6 +196,116 @@ def test_gemm_route_rejects_bad_shapes():
     assert b"masked accumulation source" in lib.dca_ops_last_error()
 
 
+# dca_ops_bn_plan, written by hand from the rule's comment in csrc/ops_api.hip ("Per-shape policy of the BN passes"):
+# (M, C, relu, res_mode, has_mask, raff) -> (lanes, apply_rows, apply_nt, raff, bwd_mode, bwd_stats_nt, bwd_rows,
+# bwd_apply_nt); bwd_mode 0 plain, 1 ReLU recomputed, 2 ReLU(bn + r) recomputed, 3 stored mask, -1 no backward.
+_P25_128, _P26_128 = 1 << 18, 1 << 19  # rows at which 128 channels reach 2^25 / 2^26 elements
+_P25_256, _P26_256 = 1 << 17, 1 << 18
+_P25_8, _P26_8 = 1 << 22, 1 << 23
+_BN_PLANS = [
+    # 8 lanes (C % 128 != 0): never non-temporal, always 256 rows, whatever the size
+    ((1, 8, 1, 0, 0, 0), (8, 256, 0, 0, 1, 0, 256, 0)),
+    ((_P25_8 - 1, 8, 1, 0, 0, 0), (8, 256, 0, 0, 1, 0, 256, 0)),
+    ((_P25_8, 8, 1, 1, 0, 0), (8, 256, 0, 0, 1, 0, 256, 0)),
+    ((_P26_8 - 1, 8, 0, 0, 0, 0), (8, 256, 0, 0, 0, 0, 256, 0)),
+    ((_P26_8, 8, 1, 2, 1, 0), (8, 256, 0, 0, 3, 0, 256, 0)),
+    ((466033, 72, 1, 2, 0, 0), (8, 256, 0, 0, 2, 0, 256, 0)),   # 72 M < 2^25
+    ((466034, 72, 1, 2, 0, 1), (8, 256, 0, 1, 2, 0, 256, 0)),   # >= 2^25
+    ((932067, 72, 0, 0, 1, 0), (8, 256, 0, 0, 3, 0, 256, 0)),   # < 2^26
+    ((932068, 72, 1, 2, 1, 1), (8, 256, 0, 1, 3, 0, 256, 0)),   # >= 2^26
+    ((246723, 136, 1, 0, 0, 0), (8, 256, 0, 0, 1, 0, 256, 0)),
+    ((246724, 136, 0, 0, 0, 0), (8, 256, 0, 0, 0, 0, 256, 0)),
+    ((493447, 136, 1, 2, 0, 0), (8, 256, 0, 0, 2, 0, 256, 0)),
+    ((493448, 136, 1, 2, 1, 0), (8, 256, 0, 0, 3, 0, 256, 0)),
+    # 16 lanes, C = 128: below 2^25 cached and 256 rows everywhere
+    ((1, 128, 1, 0, 0, 0), (16, 256, 0, 0, 1, 0, 256, 0)),
+    ((_P25_128 - 1, 128, 0, 0, 0, 0), (16, 256, 0, 0, 0, 0, 256, 0)),
+    ((_P25_128 - 1, 128, 1, 0, 0, 0), (16, 256, 0, 0, 1, 0, 256, 0)),
+    ((_P25_128 - 1, 128, 1, 2, 0, 0), (16, 256, 0, 0, 2, 0, 256, 0)),
+    ((_P25_128 - 1, 128, 1, 2, 1, 1), (16, 256, 0, 1, 3, 0, 256, 0)),
+    # [2^25, 2^26): only the backward apply changes (128 rows, non-temporal)
+    ((_P25_128, 128, 0, 0, 0, 0), (16, 256, 0, 0, 0, 0, 128, 1)),
+    ((_P25_128, 128, 1, 1, 0, 0), (16, 256, 0, 0, 1, 0, 128, 1)),
+    ((_P25_128, 128, 1, 2, 0, 1), (16, 256, 0, 1, 2, 0, 128, 1)),
+    ((_P25_128, 128, 0, 0, 1, 0), (16, 256, 0, 0, 3, 0, 128, 1)),
+    ((_P26_128 - 1, 128, 1, 0, 0, 0), (16, 256, 0, 0, 1, 0, 128, 1)),
+    ((_P26_128 - 1, 128, 1, 2, 1, 0), (16, 256, 0, 0, 3, 0, 128, 1)),
+    # >= 2^26: non-temporal everywhere, 128-row applies
+    ((_P26_128, 128, 0, 0, 0, 0), (16, 128, 1, 0, 0, 1, 128, 1)),
+    ((_P26_128, 128, 1, 0, 0, 0), (16, 128, 1, 0, 1, 1, 128, 1)),
+    ((_P26_128, 128, 1, 2, 0, 0), (16, 128, 1, 0, 2, 1, 128, 1)),
+    ((_P26_128, 128, 1, 2, 1, 0), (16, 128, 1, 0, 3, 1, 128, 1)),
+    ((_P26_128, 128, 0, 0, 1, 0), (16, 128, 1, 0, 3, 1, 128, 1)),
+    ((_P26_128, 128, 1, 2, 1, 1), (16, 128, 1, 1, 3, 1, 128, 1)),
+    # C = 256: the thresholds are on M C, not on M
+    ((_P25_256 - 1, 256, 1, 2, 1, 0), (16, 256, 0, 0, 3, 0, 256, 0)),
+    ((_P25_256, 256, 1, 2, 1, 0), (16, 256, 0, 0, 3, 0, 128, 1)),
+    ((_P26_256 - 1, 256, 1, 2, 0, 1), (16, 256, 0, 1, 2, 0, 128, 1)),
+    ((_P26_256, 256, 1, 2, 0, 1), (16, 128, 1, 1, 2, 1, 128, 1)),
+    ((_P26_256, 256, 1, 0, 0, 0), (16, 128, 1, 0, 1, 1, 128, 1)),
+    ((802816, 256, 1, 2, 1, 0), (16, 128, 1, 0, 3, 1, 128, 1)),    # ResNet-50 batch 256, layer-1 bn3
+    ((50176, 1024, 1, 2, 1, 0), (16, 256, 0, 0, 3, 0, 128, 1)),    # layer-3 bn3
+    # forms the forward has and the backward rejects (eval mode's join without ReLU; a mask anywhere else)
+    ((1000, 128, 0, 2, 0, 0), (16, 256, 0, 0, -1, 0, 256, 0)),
+    ((1000, 128, 1, 0, 1, 0), (16, 256, 0, 0, -1, 0, 256, 0)),
+    ((1000, 72, 1, 1, 1, 0), (8, 256, 0, 0, -1, 0, 256, 0)),
+    ((1000, 72, 0, 1, 1, 0), (8, 256, 0, 0, -1, 0, 256, 0)),
+]
+
+
+def test_bn_plans_match_table():
+    """dca_ops_bn_plan (csrc/ops_api.hip, no device needed) against the hand-written table above: C in {8, 72, 128,
+    136, 256}, M C on both sides of 2^25 and 2^26, the four backward modes with both legal mask uses, on-the-fly
+    residual BN on and off.  tests/test_ops_bn_gpu.py asserts the plan of every shape it runs, so a threshold change
+    that takes an instantiation out of the suite's reach fails here or there."""
+    lib, _native = _ops_lib()
+    names = [f[0] for f in _native.BnPlan._fields_]
+    assert names == ["lanes", "apply_rows", "apply_nt", "raff", "bwd_mode", "bwd_stats_nt", "bwd_rows", "bwd_apply_nt"]
+    src = open(os.path.join(nbuild.CSRC, "ops_api.hip")).read()
+    body = src[src.index("struct BnPlan {"):src.index("};", src.index("struct BnPlan {"))]
+    decl = [n.strip() for line in body.splitlines()[1:] if line.split("//")[0].strip()
+            for n in line.split("//")[0].strip().rstrip(";").replace("int ", "").split(",")]
+    assert decl == names
+    assert (_native.BWD_PLAIN, _native.BWD_RELU, _native.BWD_RES, _native.BWD_MASK) == (0, 1, 2, 3)
+    assert "enum { BWD_PLAIN = 0, BWD_RELU = 1, BWD_RES = 2, BWD_MASK = 3 };" in \
+        open(os.path.join(nbuild.CSRC, "ops_nn.hip")).read()
+    bad = []
+    for args, want in _BN_PLANS:
+        p = _native.BnPlan()
+        rc = lib.dca_ops_bn_plan(*args, ctypes.byref(p))
+        got = tuple(getattr(p, n) for n in names)
+        if rc != 0 or got != want:
+            bad.append((args, rc, got, want))
+    assert not bad, bad
+    for args, what in (((0, 128, 1, 0, 0, 0), "M >= 1"), ((100, 12, 1, 0, 0, 0), "multiple of 8"),
+                       ((100, 0, 1, 0, 0, 0), "multiple of 8"), ((100, 128, 1, 3, 0, 0), "res_mode"),
+                       ((100, 128, 1, 0, 0, 1), "on-the-fly"), ((100, 128, 1, 1, 0, 1), "on-the-fly")):
+        rc = lib.dca_ops_bn_plan(*args, ctypes.byref(_native.BnPlan()))
+        assert rc == -1 and what in lib.dca_ops_last_error().decode(), (args, rc, lib.dca_ops_last_error())
+
+
+def test_bn_bwd_rejects_unsupported_forms():
+    """dca_ops_bn_bwd refuses, before any launch (no device needed): a residual join without ReLU, a mask on any form
+    but ReLU(bn + r) or the plain BN feeding one, a join without mask and without r / dr, and a bad channel count."""
+    lib, _ = _ops_lib()
+    one = ctypes.c_void_p(256)  # a non-null pointer; a rejected call dereferences nothing
+
+    def bwd(M, C, relu, res_mode, mask, r=None, dr=None):
+        return lib.dca_ops_bn_bwd(one, one, r, one, one, one, one, one, one, one, one, dr, M, C, relu, res_mode, 0,
+                                  mask, one, None)
+    for args, what in (((64, 128, 0, 2, None, one, one), "without ReLU"),
+                       ((64, 128, 0, 2, one), "unsupported mask use"),
+                       ((64, 128, 1, 0, one), "unsupported mask use"),
+                       ((64, 72, 1, 1, one), "unsupported mask use"),
+                       ((64, 72, 0, 1, one), "unsupported mask use"),
+                       ((64, 128, 1, 2, None, one, None), "residual tensors missing"),
+                       ((64, 128, 1, 2, None, None, one), "residual tensors missing"),
+                       ((64, 12, 1, 0, None), "multiple of 8"),
+                       ((0, 128, 1, 0, None), "M >= 1")):
+        call = bwd(*args)
+        assert call == -1 and what in lib.dca_ops_last_error().decode(), (what, call, lib.dca_ops_last_error())
+
+
 def test_bn_pool_bwd_rejects_a_short_partial_buffer():
     """dca_ops_bn_pool_bwd checks the caller's partial-sum row count against ceil(N Ho Wo / 64) before any launch."""
     lib, _native = _ops_lib()

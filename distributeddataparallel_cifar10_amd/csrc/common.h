@@ -132,12 +132,18 @@ constexpr int PKW_N = PKW_STEM + 2 * 1536;
   } while (0)
 #endif
 
-// sample id of image n of the current batch, clamped into range
-__device__ __forceinline__ int sample_id(const Ctx& cx, int n) {
-  int pos = *cx.cursor + n;
-  pos = pos < 0 ? 0 : (pos >= cx.n_idx ? cx.n_idx - 1 : pos);
-  int id = cx.indices[pos];
+// sample id of image n of the current batch, clamped into range.  Two dependent loads (the cursor, then the index
+// list); a kernel that wants them apart (pks step_main) issues each itself and uses the two halves:
+// sample_pos: cursor value + n -> position in the index list; sample_clamp: the entry read there -> dataset row
+__device__ __forceinline__ int sample_pos(const Ctx& cx, int cursor, int n) {
+  const int pos = cursor + n;
+  return pos < 0 ? 0 : (pos >= cx.n_idx ? cx.n_idx - 1 : pos);
+}
+__device__ __forceinline__ int sample_clamp(const Ctx& cx, int id) {
   return id < 0 ? 0 : (id >= cx.n_data ? cx.n_data - 1 : id);
+}
+__device__ __forceinline__ int sample_id(const Ctx& cx, int n) {
+  return sample_clamp(cx, cx.indices[sample_pos(cx, *cx.cursor, n)]);
 }
 
 // conv1 weight element (co, k = ci * 9 + tap) -> its slot in the persistent stem's MFMA B fragments

@@ -158,6 +158,7 @@ __device__ __forceinline__ void pin(unsigned& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void pin(int& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void pin(uint2& x) { asm volatile("" : "+v"(x.x), "+v"(x.y)); }
 __device__ __forceinline__ void pin(uint4& x) { asm volatile("" : "+v"(x.x), "+v"(x.y), "+v"(x.z), "+v"(x.w)); }
+__device__ __forceinline__ void pin(f32x4& x) { asm volatile("" : "+v"(x)); }
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
@@ -642,9 +643,11 @@ __host__ __device__ __forceinline__ int ra_flags(int fc, int s, int chunk) {
 // The step's epoch and batch position: a chunk of C steps shares one device epoch / cursor base, advanced by C
 // (and C x B) by the reduction kernel that closes the chunk; step s of the chunk runs at base + s.
 // (The host always passes s = 0 and C = 1: every step is followed by its own reduction kernel.)
-__device__ __forceinline__ int step_epoch(const Args& pa, const RedAr& ra) {
-  return (int)(((unsigned)*pa.epoch + (unsigned)ra_s(ra)) % EPOCH_WRAP);
+// (epoch_at: the same from a device epoch the caller loaded itself -- the step's entry, step_main.)
+__device__ __forceinline__ int epoch_at(int base, const RedAr& ra) {
+  return (int)(((unsigned)base + (unsigned)ra_s(ra)) % EPOCH_WRAP);
 }
+__device__ __forceinline__ int step_epoch(const Args& pa, const RedAr& ra) { return epoch_at(*pa.epoch, ra); }
 __device__ __forceinline__ char* rbase(const RedAr& ra, int q) { return ra.peers.base[q] + xg::REGION_BYTES; }
 __device__ __forceinline__ float* rslab(const RedAr& ra, int q, int par) {
   return (float*)(rbase(ra, q) + xg::FLAG_BYTES) + (size_t)par * xg::SLAB_FLOATS;
@@ -735,10 +738,15 @@ __device__ __forceinline__ f32x4 ld4_sc1(const float* base, int bytes, int off_f
 }
 
 // trunk / stem chunk b of CH outputs in slab fragment order, summed over the nslab workgroup slabs in ONE order for
-// every block size (a 512-thread step-kernel workgroup and the 256-thread reduction kernel give bitwise-equal sums):
+// every block size (a 512-thread workgroup and the 256-thread reduction kernel give bitwise-equal sums):
 // VG = 2048 / CH virtual groups, group gv sums float4 `slot` of slabs gv, gv + VG, ... in slab order; the chunk
 // total is sum_g (acc(g) + acc(g + VG / 2)) over g < VG / 2, in g order.  A 512-thread workgroup runs one virtual
 // group per thread, a 256-thread one two (gv = grp, grp + VG / 2: it adds the pair before the LDS combine).
+// Only the reduction kernel (256 threads) ever runs this.  The 512-thread instantiation is compiled into the step
+// kernel through its fc workers' seg_process but never reached (they are handed fc1 blocks and the fc tail only); it
+// stays, in the parent's form, because the step kernel's register allocation follows it: the pinned form there cost the
+// 300-step bench 0.7 us, and compiling it out altogether (if constexpr in seg_process) lost the whole gain
+// (79.49 against the parent's 79.23 us; docs/STATUS.md, profiles/entry_roundtrips_ab.log).
 template <int NTH, int CH>
 __device__ __forceinline__ void seg_chunk(const Ctx& cx, const Args& pa, const SegLayout& Ls, int b, int nslab,
                                           float* segv, f32x4* red) {
@@ -755,19 +763,48 @@ __device__ __forceinline__ void seg_chunk(const Ctx& cx, const Args& pa, const S
 #pragma unroll
   for (int vp = 0; vp < VPG; ++vp) sacc[vp] = z4();
   for (int k0 = 0; k0 < nslab; k0 += 128) {
+    if constexpr (NTH == 256) {
+      // the reduction kernel: all VPG x NU loads of the pass in flight before the first add (one round trip per 128
+      // slabs): clamped addresses, pinned values, and adds that are selects, so no load can sink into a branch behind
+      // a full wait
+      f32x4 v[VPG][NU];
 #pragma unroll
-    for (int vp = 0; vp < VPG; ++vp) {
-      const int gv = grp + NG * vp;
-      f32x4 v[NU];
+      for (int vp = 0; vp < VPG; ++vp)
 #pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        const int k = k0 + gv + VG * u;
-        const int kc = k < nslab ? k : nslab - 1;
-        v[u] = ld4(src + (size_t)kc * stride + ec);  // plain loads: the slabs were written before the kernel boundary
+        for (int u = 0; u < NU; ++u) {
+          const int k = k0 + grp + NG * vp + VG * u;
+          const int kc = k < nslab ? k : nslab - 1;
+          v[vp][u] = ld4(src + (size_t)kc * stride + ec);  // plain loads: the slabs were written before the kernel boundary
+        }
+#pragma unroll
+      for (int vp = 0; vp < VPG; ++vp)
+#pragma unroll
+        for (int u = 0; u < NU; ++u) pin(v[vp][u]);
+#pragma unroll
+      for (int vp = 0; vp < VPG; ++vp)
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          const f32x4 tsum = sacc[vp] + v[vp][u];
+          sacc[vp] = k0 + grp + NG * vp + VG * u < nslab ? tsum : sacc[vp];
+        }
+    } else {
+      // the step kernel's fc workers (512 threads; they only ever get fc segments, this is compiled, not run): the
+      // plain form.  The pinned form here re-shaped the whole step kernel's register allocation and cost the
+      // 300-step bench 0.7 us (profiles/entry_roundtrips_ab.log, variants v1 / v5)
+#pragma unroll
+      for (int vp = 0; vp < VPG; ++vp) {
+        const int gv = grp + NG * vp;
+        f32x4 v[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          const int k = k0 + gv + VG * u;
+          const int kc = k < nslab ? k : nslab - 1;
+          v[u] = ld4(src + (size_t)kc * stride + ec);
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+          if (k0 + gv + VG * u < nslab) sacc[vp] += v[u];
       }
-#pragma unroll
-      for (int u = 0; u < NU; ++u)
-        if (k0 + gv + VG * u < nslab) sacc[vp] += v[u];
     }
   }
   red[t] = VPG == 2 ? sacc[0] + sacc[VPG - 1] : sacc[0];  // (VPG = 2: groups grp and grp + HG)
@@ -1019,10 +1056,11 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
   char* XR = U + PL::U_XR;
   unsigned short* xs = (unsigned short*)(smem + PL::O_XS);
   unsigned* codes = (unsigned*)(smem + PL::O_CODE);
-  const int epoch = step_epoch(pa, ra);
-  const int par = epoch & 1;
-  const uint8_t* my_img = pa.simg + (size_t)(par * 64 + n) * 3072;
-  const int next_id = sample_id(cx, (ra_s(ra) + 1) * B + n);
+  // Kernel entry: ONE global round trip.  The device epoch, the cursor, the step constants, the conv1 fragments, the
+  // staged image words and label of BOTH parities and the weight DMA are all issued before the stem's single wait;
+  // epoch (every round's tag), par (which staged copy is this step's) and next_id (the next batch's dataset row, from
+  // an index entry fetched after that wait and landing under the stem's MFMAs) are set there.
+  int epoch, par, next_id;
   const float Ntot = (float)B * 256.f;
   const unsigned short* pkw = (const unsigned short*)cx.pkw;
   const size_t img8 = (size_t)n * 8192 + (size_t)row * 512;  // this row inside an image of a block's tensor
@@ -1045,18 +1083,26 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     // [544,864), b2 [864,874), conv1 bias [874,906), BN shifts [906,1226)
     constexpr int NKC = 842, KCM = (NKC + NTH - 1) / NTH;
     float kc[KCM];
+    const float* ksrc[KCM];
     int lab = 0;
     // input words: thread t < 112 -> xin4 row j = t >> 3 (image row 8s-3+j), 4 columns 4 (t & 7) .., 3 channels
     const int jr = (t >> 3) < 14 ? (t >> 3) : 13, yimg = 8 * s - 3 + jr, xq = t & 7;
     const bool ivalid = t < 112 && yimg >= 0 && yimg < 32;
-    const unsigned* imw = (const unsigned*)my_img;
     const int yc = yimg < 0 ? 0 : (yimg > 31 ? 31 : yimg);
-    unsigned iw0 = 0u, iw1 = 0u, iw2 = 0u;
+    // both staging parities (4 more dwords, live in this phase only), selected by par after the wait: the other
+    // parity's slot is written by this image's own workgroups at the END of a step (no workgroup gets there before
+    // every one has passed this point: 20 all-to-all BatchNorm rounds lie between), and its value is discarded
+    unsigned iwp[2][3];
+    int labp[2];
     auto image_loads = [&] {
-      lab = pa.slab[par * 64 + n];
-      iw0 = imw[yc * 8 + xq];
-      iw1 = imw[256 + yc * 8 + xq];
-      iw2 = imw[512 + yc * 8 + xq];
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const unsigned* imw = (const unsigned*)(pa.simg + (size_t)(p * 64 + n) * 3072);
+        labp[p] = pa.slab[p * 64 + n];
+        iwp[p][0] = imw[yc * 8 + xq];
+        iwp[p][1] = imw[256 + yc * 8 + xq];
+        iwp[p][2] = imw[512 + yc * 8 + xq];
+      }
     };
 #pragma unroll
     for (int m = 0; m < KCM; ++m) {
@@ -1071,12 +1117,12 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
                        : k < 490 ? cx.params + OFF_FC2B + (k - 480)
                        : k < 522 ? cx.params + OFF_C1B + (k - 490)
                                  : (const float*)cx.STATS + 2 * (k - 522);
-      kc[m] = *src;
+      ksrc[m] = src;
     }
-    image_loads();  // (after the constants: the round-4 order)
-    // forward trunk weights, records [tap][co] x ci (hi, lo); RES: the dgrad weights too, records [8 - tap][ci] x co
-    wt_dma<P>(WT, pkw, wv, lane);
-    if constexpr (PL::RES) wt_dma<P>(WTD, pkw + PKW_DGRAD, wv, lane);
+    // (the constants' addresses first: a branchy select the compiler guards with vmcnt waits once a load is in flight)
+    const int ep_raw = *pa.epoch;  // the first load, and not waited on alone: nothing below needs it for an address
+#pragma unroll
+    for (int m = 0; m < KCM; ++m) kc[m] = *ksrc[m];
     uint2 bwr[P + 1][2][3];        // conv1 B fragments: lane (co = 16h + c, k-group q) of MFMA m
 #pragma unroll
     for (int p = 0; p <= P; ++p)
@@ -1085,12 +1131,32 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
 #pragma unroll
         for (int m = 0; m < 3; ++m)
           bwr[p][h][m] = ((const uint2*)(pkw + PKW_STEM + p * 1536))[(h * 3 + m) * 64 + lane];
+    int cur = *cx.cursor;  // first half of sample_id (the next batch); its index entry is fetched after the wait
+    image_loads();
+    // forward trunk weights, records [tap][co] x ci (hi, lo); RES: the dgrad weights too, records [8 - tap][ci] x co
+    // (last: the compiler waits for vmcnt(0) before any LDS store while a DMA is in flight, so nothing may follow it)
+    wt_dma<P>(WT, pkw, wv, lane);
+    if constexpr (PL::RES) wt_dma<P>(WTD, pkw + PKW_DGRAD, wv, lane);
+    int epr = ep_raw;
+    pin(epr);
 #pragma unroll
     for (int m = 0; m < KCM; ++m) pin(kc[m]);
-    pin(lab);
-    pin(iw0);
-    pin(iw1);
-    pin(iw2);
+    pin(cur);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      pin(labp[p]);
+      pin(iwp[p][0]);
+      pin(iwp[p][1]);
+      pin(iwp[p][2]);
+    }
+    // (pin() hands back a VGPR the compiler takes for divergent: the three workgroup-uniform words go back to SGPRs,
+    // where the loads of a uniform address had them, or every tag and poll compare of the step turns into vector code)
+    epoch = epoch_at(__builtin_amdgcn_readfirstlane(epr), ra);
+    cur = __builtin_amdgcn_readfirstlane(cur);
+    par = epoch & 1;
+    lab = par ? labp[1] : labp[0];
+    const unsigned iw0 = par ? iwp[1][0] : iwp[0][0], iw1 = par ? iwp[1][1] : iwp[0][1];
+    const unsigned iw2 = par ? iwp[1][2] : iwp[0][2];
 #pragma unroll
     for (int p = 0; p <= P; ++p)
 #pragma unroll
@@ -1130,6 +1196,9 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's weight DMA has landed in LDS
     lds_barrier();
     DCA_STAMP(cx, 0, L, 2);
+    // second half of sample_id: the index entry of the next batch's image n, issued with no other load in flight (the
+    // stem loop issues no VM op) and landed long before the stem ends, where it is pinned
+    int nid = cx.indices[sample_pos(cx, cur, (ra_s(ra) + 1) * B + n)];
     s4v bw[P + 1][2][3];
 #pragma unroll
     for (int p = 0; p <= P; ++p)
@@ -1192,6 +1261,8 @@ __device__ __forceinline__ void step_main(const Ctx& cx, const Args& pa, const R
     }
     lds_barrier();
     DCA_STAMP(cx, 0, L, 3);
+    pin(nid);
+    next_id = sample_clamp(cx, __builtin_amdgcn_readfirstlane(nid));
     unsigned cw = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

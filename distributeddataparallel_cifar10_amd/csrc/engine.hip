@@ -23,6 +23,7 @@
 #include "xgmi_allreduce.hip"
 #include "netresdeep_pks.hip"
 #include "netresdeep_eval.hip"
+#include "engine_plan.h"
 
 namespace {
 
@@ -108,8 +109,7 @@ struct Engine {
   std::map<int, hipGraphExec_t> graphs;
   bool persistent = false;  // the image-sliced persistent step kernel (netresdeep_pks.hip; default)
   pks::Args qa{};
-  bool comm_on = false;  // the step ends with a gradient collective (world_size > 1, or force_comm)
-  int resident = 0;      // persistent engine: live step workgroups allowed in one grid (coresident_budget, 1 rank)
+  bool comm_on = false;  // the step ends with a gradient collective (dca::comm_on: world_size > 1, or force_comm)
   int per_cu = 0, ncu = 0;  // persistent engine: step workgroups per CU (occupancy) and CUs of the device
   int staged_b = 0;  // persistent engine: batch slots of the current staging parity that hold the next batch
   int last_b = 0;    // batch size of the last enqueued step (BN slots are re-zeroed when it changes)
@@ -119,10 +119,17 @@ struct Engine {
   int shared_device = 0;  // set by the host: number of xGMI ranks on this device (shared-GPU rehearsal; 0/1: not
                           // shared): the coarse 107-segment layout, and fc workers only when every co-scheduled
                           // grid fits (fc_in_step_for), so a spinning kernel always leaves CUs for a peer's step
-  std::map<std::string, void*> regions;
-  // dynamic LDS sizes
-  size_t s_stem = 0, s_fwd = 0, s_head1 = 0, s_head2 = 0, s_dgrad = 0, s_dgrad0 = 0, s_wgrad = 0, s_fc = 0;
-  // kernel entry points for the selected (BF, R, RW) instantiation
+  // The workspace: one table drives allocation, offsets, the name lookup and the pointer binding (alloc_workspace)
+  struct Region {
+    const char* name;
+    size_t bytes;
+    void** dst;           // the Ctx / pks::Args / Peers field that points at the region (null: reached by name only)
+    char* ptr = nullptr;  // 256-byte aligned, in table order
+  };
+  std::vector<Region> regions;
+  // kernel entry points for the selected (BF, R, RW) instantiation; their LDS sizes are the plan's (engine_plan.h)
+  void (*kstep)(Ctx, pks::Args, pks::RedAr) = nullptr;
+  void (*kxgmi)(Ctx, xg::Peers, const float*, float*, unsigned*, int, unsigned long long) = nullptr;
   void (*kstem)(Ctx) = nullptr;
   void (*kfwd)(Ctx, int) = nullptr;
   void (*khead1)(Ctx) = nullptr;
@@ -140,24 +147,49 @@ struct Engine {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The kernels chosen by the dtype alone (named in this order, the compiler keeps the code object's kernel order)
+static void bind_dtype_kernels(Engine* e) {
+  e->kstep = e->bf ? pks::k_pks_step<0> : pks::k_pks_step<1>;
+  e->kxgmi = e->bf ? xg::k_xgmi_ar_sgd<true> : xg::k_xgmi_ar_sgd<false>;
+}
 template <bool BF, int R, int RW>
 static void bind_kernels(Engine* e) {
   e->kstem = k_stem_block0<BF, R>;
   e->kfwd = k_fwd_block<BF, R>;
   e->khead1 = k_head1<R>;
   e->khead2 = k_head2<R>;
-  using L = LdsPlan<BF, R, RW>;
-  e->s_stem = L::stem;
-  e->s_fwd = L::fwd;
-  e->s_head1 = L::head1;
-  e->s_head2 = L::head2;
-  e->s_dgrad = L::dgrad;
-  e->s_dgrad0 = L::dgrad0;
-  e->s_wgrad = L::wgrad;
-  e->s_fc = L::fc;
   e->kbwd = k_bwd_block<BF, R, RW>;
   e->kred = k_reduce<BF>;
   e->kapply = k_apply_sgd<BF>;
+}
+
+// What the step plan reads of this engine (engine_plan.h)
+static PlanIn plan_in(const Engine* e) {
+  const DcaInit& in = e->in;
+  PlanIn p{};
+  p.persistent = e->persistent;
+  p.bf16 = e->bf;
+  p.rows = in.rows;
+  p.world_size = in.world_size;
+  p.comm_mode = in.comm_mode;
+  p.force_comm = in.force_comm;
+  p.loopback = in.loopback;
+  p.opt_on = e->opt_on;
+  p.shared_device = e->shared_device;
+  p.fc_in_step = e->fc_in_step;
+  p.per_cu = e->per_cu;
+  p.ncu = e->ncu;
+  p.full_device = !in.auto_engine;
+  p.bmax = in.bmax;
+  return p;
+}
+// engine_plan with the engine's error convention: -1 and the reason in g_err when the step cannot run
+static int plan_step(const PlanIn& in, int B, int part, StepPlan* p) {
+  if (const char* why = engine_plan(in, B, part, p)) {
+    g_err = why;
+    return -1;
+  }
+  return 0;
 }
 
 static int alloc_workspace(Engine* e) {
@@ -165,134 +197,91 @@ static int alloc_workspace(Engine* e) {
   const size_t pstride = bmax * e->TPI;
   const size_t nslab = 9 * bmax * (16 / e->RW) + pstride;
   const size_t esz = e->bf ? 2 : 4;
-  struct R_ {
-    const char* name;
-    size_t bytes;
-  } regs[] = {
-      {"X", 10 * bmax * 8192 * 4},   {"Y", 10 * bmax * 8192 * 4},     {"DY", 10 * bmax * 8192 * 4},
-      {"G", 2 * bmax * 8192 * 4},    {"SCODE", bmax * 8192},          {"FPART", 10 * pstride * 32 * 8},
-      {"STATS", 10 * 32 * 8},        {"BPART", 2 * pstride * 32 * 8}, {"WSLAB", nslab * WSLAB_N * 4},
-      {"SSLAB", pstride * SSLAB_N * 4}, {"HP", bmax * 2048 * 4},      {"HH", bmax * 32 * 4},
-      {"HDH", bmax * 32 * 4},        {"HDL", bmax * 16 * 4},          {"HLOSS", bmax * 4},
-      {"HPART", pstride * 32 * 4},   {"HCODE", bmax * 2048},
-      {"WT_F", 9216 * esz},          {"WT_D", 9216 * esz},            {"SW", 1024 * esz},
-      {"RS_BASE", 64 * 4},           {"CURSOR", 16},                  {"STEPS", 16},
-      {"LOSS", 16},                  {"STAMPS", 32 * 256 * 8 * 2 * 8},
-      {"EPOCH", 16},                 {"ERR", 16},
-      {"TSLAB", bmax * pks::S * WSLAB_N * 4}, {"BNG", 64 * 4}, {"W1B", 65536 * 2}, {"SIMG", 2 * 64 * 3072},
-      {"SLAB", 2 * 64 * 4},
-      {"COMMT", 16}, {"PKW", PKW_N * 2},
-      {"PKS_GRAN", 2 * (size_t)pks::LMAX * pks::GSTR * 8}, {"PKS_YH", 10 * (size_t)pks::LMAX * 2 * 512 * 4},
-      {"PKS_BNX", 2 * (size_t)pks::LMAX * 64 * 4},
-      {"PKS_HDONE", (size_t)pks::LMAX * 8},  // head-done granules
-      {"C1", e->in.debug ? bmax * 32 * 1024 * 4 : 16},
+  Ctx& c = e->base;
+  pks::Args& qa = e->qa;
+#define TO(field) (void**)&(field)
+  e->regions = {
+      {"X", 10 * bmax * 8192 * 4, TO(c.X)},
+      {"Y", 10 * bmax * 8192 * 4, TO(c.Y)},
+      {"DY", 10 * bmax * 8192 * 4, TO(c.DY)},
+      {"G", 2 * bmax * 8192 * 4, TO(c.G)},
+      {"SCODE", bmax * 8192, TO(c.SCODE)},
+      {"FPART", 10 * pstride * 32 * 8, TO(c.FPART)},
+      {"STATS", 10 * 32 * 8, TO(c.STATS)},
+      {"BPART", 2 * pstride * 32 * 8, TO(c.BPART)},
+      {"WSLAB", nslab * WSLAB_N * 4, TO(c.WSLAB)},
+      {"SSLAB", pstride * SSLAB_N * 4, TO(c.SSLAB)},
+      {"HP", bmax * 2048 * 4, TO(c.HP)},
+      {"HH", bmax * 32 * 4, TO(c.HH)},
+      {"HDH", bmax * 32 * 4, TO(c.HDH)},
+      {"HDL", bmax * 16 * 4, TO(c.HDL)},
+      {"HLOSS", bmax * 4, TO(c.HLOSS)},
+      {"HPART", pstride * 32 * 4, TO(c.HPART)},
+      {"HCODE", bmax * 2048, TO(c.HCODE)},
+      {"WT_F", 9216 * esz, TO(c.wt_f)},
+      {"WT_D", 9216 * esz, TO(c.wt_d)},
+      {"SW", 1024 * esz, TO(c.sw)},
+      {"RS_BASE", 64 * 4, TO(c.rs_base)},
+      {"CURSOR", 16, TO(c.cursor)},
+      {"STEPS", 16, TO(c.step_count)},
+      {"LOSS", 16, TO(c.loss_acc)},
+      {"STAMPS", 32 * 256 * 8 * 2 * 8, TO(c.stamps)},
+      {"EPOCH", 16, TO(qa.epoch)},
+      {"ERR", 16, TO(qa.err)},
+      {"TSLAB", bmax * pks::S * WSLAB_N * 4, TO(qa.tslab)},
+      {"BNG", 64 * 4, TO(qa.bng)},
+      {"W1B", 65536 * 2, TO(c.w1b)},
+      {"SIMG", 2 * 64 * 3072, TO(qa.simg)},
+      {"SLAB", 2 * 64 * 4, TO(qa.slab)},
+      {"COMMT", 16, TO(e->peers.ticks)},
+      {"PKW", PKW_N * 2, TO(c.pkw)},
+      {"PKS_GRAN", 2 * (size_t)pks::LMAX * pks::GSTR * 8, TO(qa.gran)},
+      {"PKS_YH", 10 * (size_t)pks::LMAX * 2 * 512 * 4, TO(qa.yh)},
+      {"PKS_BNX", 2 * (size_t)pks::LMAX * 64 * 4, TO(qa.bnx)},
+      {"PKS_HDONE", (size_t)pks::LMAX * 8, TO(qa.hdone)},  // head-done granules
+      {"C1", e->in.debug ? bmax * 32 * 1024 * 4 : 16, TO(qa.c1)},
   };
+#undef TO
   size_t total = 0;
-  for (auto& r : regs) total += align_up(r.bytes, 256);
+  for (auto& r : e->regions) total += align_up(r.bytes, 256);
   HIPCK(hipMalloc(&e->wsp, total));
   HIPCK(hipMemset(e->wsp, 0, total));
   e->ws_bytes = total;
   size_t off = 0;
-  for (auto& r : regs) {
-    e->regions[r.name] = e->wsp + off;
+  for (auto& r : e->regions) {
+    r.ptr = e->wsp + off;
+    if (r.dst) *r.dst = r.ptr;
     off += align_up(r.bytes, 256);
   }
-  Ctx& c = e->base;
-  c.X = (float*)e->regions["X"];
-  c.Y = (float*)e->regions["Y"];
-  c.DY = (float*)e->regions["DY"];
-  c.G = (float*)e->regions["G"];
-  c.SCODE = (uint8_t*)e->regions["SCODE"];
-  c.FPART = (float2*)e->regions["FPART"];
-  c.STATS = (float2*)e->regions["STATS"];
-  c.BPART = (float2*)e->regions["BPART"];
-  c.WSLAB = (float*)e->regions["WSLAB"];
-  c.SSLAB = (float*)e->regions["SSLAB"];
-  c.HP = (float*)e->regions["HP"];
-  c.HH = (float*)e->regions["HH"];
-  c.HDH = (float*)e->regions["HDH"];
-  c.HDL = (float*)e->regions["HDL"];
-  c.HLOSS = (float*)e->regions["HLOSS"];
-  c.HPART = (float*)e->regions["HPART"];
-  c.HCODE = (uint8_t*)e->regions["HCODE"];
-  c.wt_f = e->regions["WT_F"];
-  c.wt_d = e->regions["WT_D"];
-  c.sw = e->regions["SW"];
-  c.rs_base = (float*)e->regions["RS_BASE"];
-  c.cursor = (int*)e->regions["CURSOR"];
-  c.step_count = (int*)e->regions["STEPS"];
-  c.loss_acc = (double*)e->regions["LOSS"];
   c.pstride = (int)pstride;
-  c.stamps = (unsigned long long*)e->regions["STAMPS"];
+  qa.debug = e->in.debug;
   // derived weight copies: each engine writes only the layouts its kernels read (derive_param skips null ones)
   c.swf = nullptr;
-  if (e->persistent) {
-    c.w1b = e->regions["W1B"];
-    c.pkw = (unsigned short*)e->regions["PKW"];
-    c.wt_f = c.wt_d = c.sw = nullptr;
-  } else {
-    c.w1b = nullptr;
-    c.pkw = nullptr;
-  }
-  pks::Args& qa = e->qa;
-  qa.gran = (unsigned long long*)e->regions["PKS_GRAN"];
-  qa.bnx = (unsigned*)e->regions["PKS_BNX"];
-  qa.hdone = (unsigned long long*)e->regions["PKS_HDONE"];
-  qa.epoch = (int*)e->regions["EPOCH"];
-  qa.err = (unsigned*)e->regions["ERR"];
-  qa.tslab = (float*)e->regions["TSLAB"];
-  qa.bng = (float*)e->regions["BNG"];
-  qa.simg = (uint8_t*)e->regions["SIMG"];
-  qa.slab = (int*)e->regions["SLAB"];
-  qa.yh = (float*)e->regions["PKS_YH"];
-  qa.c1 = (float*)e->regions["C1"];
-  qa.debug = e->in.debug;
+  if (e->persistent) c.wt_f = c.wt_d = c.sw = nullptr;
+  else c.w1b = c.pkw = nullptr;
   return 0;
 }
 
 static int set_lds_limits(Engine* e) {
-  const size_t dg = std::max(std::max(e->s_dgrad, e->s_dgrad0), std::max(e->s_wgrad, e->s_fc));
-  HIPCK(hipFuncSetAttribute((const void*)e->kstem, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->s_stem));
-  HIPCK(hipFuncSetAttribute((const void*)e->kfwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->s_fwd));
-  HIPCK(hipFuncSetAttribute((const void*)e->khead1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->s_head1));
-  HIPCK(hipFuncSetAttribute((const void*)e->khead2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->s_head2));
-  HIPCK(hipFuncSetAttribute((const void*)e->kbwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dg));
-  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            pks::Plan<0>::TOTAL));
-  HIPCK(hipFuncSetAttribute((const void*)pks::k_pks_step<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            pks::Plan<1>::TOTAL));
+  const MkLds L = mk_lds(e->bf, e->R);
+  const int lds[] = {L.stem, L.fwd, L.head1, L.head2, std::max(std::max(L.dgrad, L.dgrad0), std::max(L.wgrad, L.fc)),
+                     e->bf ? pks::Plan<0>::TOTAL : pks::Plan<1>::TOTAL};
+  const void* fn[] = {(const void*)e->kstem,  (const void*)e->kfwd, (const void*)e->khead1,
+                      (const void*)e->khead2, (const void*)e->kbwd, (const void*)e->kstep};
+  for (int i = 0; i < 6; ++i) HIPCK(hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds[i]));
   return 0;
 }
 
-// comm_mode 2: the one-shot xGMI all-reduce fused with the averaging SGD (replaces all-reduce + k_apply_sgd)
-static int enqueue_xgmi_sgd(Engine* e, const Ctx& cx) {
-  if (!e->peers_open) {
-    g_err = "xGMI all-reduce: peers not mapped (call dca_engine_ipc_open first)";
-    return -1;
-  }
-  if (e->bf)
-    hipLaunchKernelGGL(xg::k_xgmi_ar_sgd<true>, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, e->peers,
-                       (const float*)cx.grads, (float*)nullptr, e->qa.err + 1, 1, e->ar_deadline);
-  else
-    hipLaunchKernelGGL(xg::k_xgmi_ar_sgd<false>, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, e->peers,
-                       (const float*)cx.grads, (float*)nullptr, e->qa.err + 1, 1, e->ar_deadline);
-  HIPCK(hipGetLastError());
-  return 0;
+// comm_mode 2: the one-shot xGMI all-reduce of `src` over the peers P.  sgd 1: fused with the averaging SGD (replaces
+// all-reduce + k_apply_sgd); sgd 0: the sum (CC4 tail included) lands in dst
+static void launch_xgmi(Engine* e, const Ctx& cx, const xg::Peers& P, const float* src, float* dst, int sgd,
+                        unsigned long long deadline) {
+  hipLaunchKernelGGL(e->kxgmi, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, P, src, dst, e->qa.err + 1, sgd, deadline);
 }
-
-// Optimiser mode, comm_mode 2: the same one-shot all-reduce without the update -- the summed gradient (CC4 tail
-// included) lands in cx.grads, k_apply_opt follows
-static int enqueue_xgmi_sum(Engine* e, const Ctx& cx) {
-  if (!e->peers_open) {
-    g_err = "xGMI all-reduce: peers not mapped (call dca_engine_ipc_open first)";
-    return -1;
-  }
-  if (e->bf)
-    hipLaunchKernelGGL(xg::k_xgmi_ar_sgd<true>, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, e->peers,
-                       (const float*)cx.grads, cx.grads, e->qa.err + 1, 0, e->ar_deadline);
-  else
-    hipLaunchKernelGGL(xg::k_xgmi_ar_sgd<false>, dim3(xg::AR_NB), dim3(xg::AR_T), 0, e->st, cx, e->peers,
-                       (const float*)cx.grads, cx.grads, e->qa.err + 1, 0, e->ar_deadline);
+// A step's xGMI all-reduce of its gradient.  apply: with the averaging SGD; else summed into dst (optimiser mode:
+// cx.grads, k_apply_opt follows)
+static int enqueue_xgmi(Engine* e, const Ctx& cx, float* dst, int apply) {
+  launch_xgmi(e, cx, e->peers, cx.grads, dst, apply, e->ar_deadline);
   HIPCK(hipGetLastError());
   return 0;
 }
@@ -304,191 +293,115 @@ static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
   return 0;
 }
 
-// Persistent path: the sliced step kernel, then ONE kernel for reduction + all-reduce + SGD (mode: see
-// k_pks_reduce_ar).  `part`: 0 = the whole step; 1 = compute up to (not including) the gradient all-reduce;
-// 2 = what follows it (averaging SGD + CC4 base).  Parts 1/2 exist for comm_mode 1, where the host runs the
-// all-reduce in between.
-// grid of the sliced step: S workgroups per image, image slots rounded up to a multiple of 8 (see k_pks_step)
-static int pks_grid(int B) { return (B + 7) / 8 * 8 * pks::S; }
-// the step workgroups that stay resident and spin in its exchanges (the padding ids of pks_grid exit at once)
-static int pks_live(int B) { return B * pks::S; }
+// RCCL, multi-kernel engine: bucket B (everything behind bucket A) is all-reduced on the comm stream once the
+// reduction has written it, and the step's stream waits for it
+static int enqueue_bucket_b(Engine* e, const Ctx& cx) {
+  HIPCK(hipEventRecord(e->evB, e->st));
+  HIPCK(hipStreamWaitEvent(e->cst, e->evB, 0));
+  NCCK(ncclAllReduce(cx.grads + OFF_CONVW, cx.grads + OFF_CONVW, FLAT_N - OFF_CONVW, ncclFloat32, ncclSum, e->comm,
+                     e->cst));
+  HIPCK(hipEventRecord(e->evC, e->cst));
+  HIPCK(hipStreamWaitEvent(e->st, e->evC, 0));
+  return 0;
+}
 
-// Co-residency budget: how many spinning workgroups ONE rank may have resident at once -- one rule for a device of
-// its own and a device shared by n ranks (the shared-GPU rehearsal).  Every workgroup of a persistent grid must be
-// resident together; the occupancy answer can be one block per CU high near register edges (MI355X guide,
-// Residency), so a margin stays free: one block per CU when several fit, else one CU -- unless the caller asked
-// for the whole (dedicated) device explicitly.  Ranks sharing the device split what is left evenly: a rank's step
-// (+ fc workers) and its reduction grid stay within its share, so a late rank always finds room for its step
-// however the others are spread over their steps and reductions.  (Before round 5 the shared share was
-// slots / n with no margin; 8 ranks x batch 8 filled it exactly and a BN exchange timed out.)
-// Mirrored in Python: runtime/engine.py coresident_budget (CPU-tested).
-static int coresident_budget(int per_cu, int ncu, int n_share, bool full_device) {
-  const int slots = per_cu * ncu;
-  const int margin = per_cu > 1 ? ncu : (full_device && n_share <= 1 ? 0 : 1);
-  return (slots - margin) / std::max(n_share, 1);
-}
-static int share_budget(const Engine* e) {
-  return e->shared_device > 1 ? coresident_budget(e->per_cu, e->ncu, e->shared_device, false) : e->resident;
-}
-// gradient-segment layout (pks::seg_layout): trunk / conv1 chunks of 128 elements, 256 on a shared device (fewer
-// reduction workgroups: they must leave CUs for a peer's step)
-static int seg_ch(const Engine* e) { return e->shared_device > 1 ? 256 : 128; }
-
-// Whether the step at batch B runs the fc gradient segments on fc workers (the live step + N_FCW fits the budget).
-static bool fc_in_step_for(const Engine* e, int B) {
-  return e->fc_in_step && pks_live(B) + pks::N_FCW <= share_budget(e);
-}
-// Reduction grid: one workgroup per segment + the bookkeeping one; shared device: capped at the rank's budget
-// (k_pks_reduce_ar then loops over the segments).
-static int reduce_grid(const Engine* e, int nred_plus) {
-  return e->shared_device > 1 ? std::min(nred_plus, share_budget(e)) : nred_plus;
+// What follows the gradient reduction (StepTail): the collective on the reduced gradient, then the update.  RCCL: the
+// sliced engine all-reduces the whole buffer on its own stream; the multi-kernel engine has bucket A in flight
+// already (enqueue_step) and adds bucket B.
+static int enqueue_tail(Engine* e, const Ctx& cx, int tail) {
+  if (tail == TAIL_XGMI_SGD) return enqueue_xgmi(e, cx, nullptr, 1);
+  if (tail == TAIL_XGMI_OPT && enqueue_xgmi(e, cx, cx.grads, 0)) return -1;
+  if (tail == TAIL_RCCL_SGD || tail == TAIL_RCCL_OPT) {
+    if (e->persistent) NCCK(ncclAllReduce(cx.grads, cx.grads, FLAT_N, ncclFloat32, ncclSum, e->comm, e->st));
+    else if (enqueue_bucket_b(e, cx)) return -1;
+  }
+  if (tail == TAIL_XGMI_OPT || tail == TAIL_RCCL_OPT || tail == TAIL_OPT) return enqueue_apply_opt(e, cx);
+  if (tail == TAIL_RCCL_SGD || tail == TAIL_SGD) hipLaunchKernelGGL(e->kapply, dim3(64), dim3(NT), 0, e->st, cx, 1);
+  HIPCK(hipGetLastError());
+  return 0;
 }
 
 // The segment arguments of a sliced launch (pks::RedAr): the peers' regions, the exchange's error word and deadline,
 // the segment mode, the flags word and the segment layout.
-static pks::RedAr red_args(const Engine* e, int mode, int flags, unsigned long long deadline) {
+static pks::RedAr red_args(const Engine* e, int mode, int flags, int seg_ch, unsigned long long deadline) {
   pks::RedAr ra{};
   ra.peers = e->peers;
   ra.err = e->qa.err + 1;
   ra.deadline = deadline;
   ra.mode = mode;
   ra.fc_in_step = flags;
-  ra.seg_ch = seg_ch(e);
+  ra.seg_ch = seg_ch;
   return ra;
 }
-// Segment mode of a training step: 0 fused SGD (world size 1), 1 gradient only (RCCL / host all-reduce, or the
-// optimiser pass: fc workers included), 2 the xGMI exchange + averaging SGD.
-static int train_mode(const Engine* e) {
-  if (e->opt_on) return 1;
-  if (!e->comm_on) return 0;
-  return e->in.comm_mode == 2 ? 2 : 1;
+// Mode 3, the exchange self-test: the pattern `src` travels through the segments' protocol into `dst` (outside the
+// training comm-time counters)
+static pks::RedAr selftest_redar(const Engine* e, const float* src, float* dst, int flags,
+                                 unsigned long long deadline) {
+  pks::RedAr ra = red_args(e, 3, flags, seg_ch(plan_in(e)), deadline);
+  ra.peers.ticks = nullptr;
+  ra.st_src = src;
+  ra.st_dst = dst;
+  ra.st_n = FLAT_N;
+  return ra;
 }
 
-// The sliced step kernel.
-static int enqueue_pks_step(Engine* e, int B) {
+// The sliced engine's reduction kernel in the plan's form (k_pks_reduce_ar<0|1|2>)
+static void launch_reduce_ar(Engine* e, int form, int grid, int lds, const Ctx& cx, int nslab, const pks::RedAr& ra) {
+  auto* k = pks::k_pks_reduce_ar<1>;
+  if (form == 2) k = pks::k_pks_reduce_ar<2>;
+  if (form == 0) k = pks::k_pks_reduce_ar<0>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, e->st, cx, e->qa, nslab, ra);
+}
+// The same kernel as the self-test runs it: every segment exchanged in the reduction kernel, batch 1
+static void launch_selftest_reduce(Engine* e, const pks::RedAr& ra) {
   Ctx cx = e->base;
-  cx.B = B;
-  if (e->comm_on && e->in.comm_mode == 2 && !e->peers_open) {
+  cx.B = 1;
+  launch_reduce_ar(e, 0, reduce_grid(plan_in(e), pks::seg_layout(ra.seg_ch).nseg), pks::stage_floats(1) * 4, cx, 1, ra);
+}
+
+// Enqueue one training step for batch B on e->st (and e->cst for the multi-kernel engine's collectives): plan, then
+// launch what the plan says.  `part`: see engine_plan.
+static int enqueue_step(Engine* e, int B, int part = 0) {
+  StepPlan p;
+  if (plan_step(plan_in(e), B, part, &p)) return -1;
+  if (part != 2 && e->comm_on && e->in.comm_mode == 2 && !e->peers_open) {
     g_err = "xGMI all-reduce: peers not mapped (call dca_engine_ipc_open first)";
     return -1;
   }
-  if (pks_live(B) > share_budget(e)) {  // (set_shared_device already refused batch_max; kept as the last guard)
-    g_err = "persistent engine: " + std::to_string(pks_live(B)) + " step workgroups (batch " + std::to_string(B) +
-            ") exceed the co-residency budget of " + std::to_string(share_budget(e)) + " per rank";
-    return -1;
-  }
-  const bool fc = fc_in_step_for(e, B);
-  const pks::RedAr ra = red_args(e, train_mode(e), pks::ra_flags(fc, 0, 0), e->ar_deadline);
-  const dim3 grid(pks_grid(B) + (fc ? pks::N_FCW : 0));
-  const dim3 blk(pks::NTH);
-  if (e->bf)
-    hipLaunchKernelGGL((pks::k_pks_step<0>), grid, blk, pks::Plan<0>::TOTAL, e->st, cx, e->qa, ra);
-  else
-    hipLaunchKernelGGL((pks::k_pks_step<1>), grid, blk, pks::Plan<1>::TOTAL, e->st, cx, e->qa, ra);
-  HIPCK(hipGetLastError());
-  return 0;
-}
-
-// The reduction kernel after a step (its segments + its bookkeeping, epoch and cursor advanced by one step); then,
-// RCCL / host all-reduce (mode 1), the collective and the averaging SGD.
-// part: 0 whole; 1 up to the all-reduce; 2 the SGD after it (comm_mode 1, the host runs the all-reduce between).
-static int enqueue_pks_reduce(Engine* e, int B, int part) {
   Ctx cx = e->base;
   cx.B = B;
-  const bool multi = e->comm_on, xgmi = multi && e->in.comm_mode == 2;
-  if (part != 2) {
-    const bool fc = fc_in_step_for(e, B);
-    const pks::RedAr ra = red_args(e, train_mode(e), pks::ra_flags(fc, 0, 1), e->ar_deadline);
-    const dim3 rgrid(reduce_grid(e, pks::reduce_segments(fc, ra.seg_ch) + 1));
-    // the lean forms (no fc segments, one exchange mode): world size 1, or the xGMI exchange (also on a shared
-    // device, so the multi-rank rehearsals run the form a multi-GPU node runs)
-    const int lean = !fc ? 0 : (ra.mode == 0 ? 1 : (ra.mode == 2 ? 2 : 0));
-    const size_t lds = pks::stage_floats(B) * 4;
-    if (lean == 1)
-      hipLaunchKernelGGL(pks::k_pks_reduce_ar<1>, rgrid, dim3(256), lds, e->st, cx, e->qa, B * pks::S, ra);
-    else if (lean == 2)
-      hipLaunchKernelGGL(pks::k_pks_reduce_ar<2>, rgrid, dim3(256), lds, e->st, cx, e->qa, B * pks::S, ra);
-    else
-      hipLaunchKernelGGL(pks::k_pks_reduce_ar<0>, rgrid, dim3(256), lds, e->st, cx, e->qa, B * pks::S, ra);
+  if (e->persistent) {
+    // the sliced step kernel, then ONE kernel for reduction + all-reduce + SGD (mode: see k_pks_reduce_ar); its
+    // segments + its bookkeeping, epoch and cursor advanced by one step
+    if (part != 2) {
+      pks::RedAr ra = red_args(e, p.mode, pks::ra_flags(p.fc, 0, 0), p.seg_ch, e->ar_deadline);
+      hipLaunchKernelGGL(e->kstep, dim3(p.step_grid), dim3(p.step_block), p.step_lds, e->st, cx, e->qa, ra);
+      HIPCK(hipGetLastError());
+      ra.fc_in_step = pks::ra_flags(p.fc, 0, 1);
+      launch_reduce_ar(e, p.reduce_form, p.reduce_grid, p.reduce_lds, cx, B * pks::S, ra);
+    }
+    return enqueue_tail(e, cx, p.tail);
   }
-  if (e->opt_on) {  // split form: the collective on the unapplied gradient, then the optimiser pass
-    if (multi && xgmi && part == 0 && enqueue_xgmi_sum(e, cx)) return -1;
-    if (multi && !xgmi && part == 0)
-      NCCK(ncclAllReduce(cx.grads, cx.grads, FLAT_N, ncclFloat32, ncclSum, e->comm, e->st));
-    if (part != 1 && enqueue_apply_opt(e, cx)) return -1;
-  } else if (multi && !xgmi) {  // RCCL (comm_mode 0, captured) or the host (comm_mode 1, between parts 1 and 2)
-    if (part == 0) NCCK(ncclAllReduce(cx.grads, cx.grads, FLAT_N, ncclFloat32, ncclSum, e->comm, e->st));
-    if (part != 1) hipLaunchKernelGGL(e->kapply, dim3(64), dim3(NT), 0, e->st, cx, 1);
-  }
-  HIPCK(hipGetLastError());
-  return 0;
-}
-
-// One step followed by its own reduction.
-static int enqueue_step_persistent(Engine* e, int B, int part) {
-  if (part != 2 && enqueue_pks_step(e, B)) return -1;
-  return enqueue_pks_reduce(e, B, part);
-}
-
-// Enqueue one full training step for batch B on e->st (and e->cst for the collectives).
-static int enqueue_step(Engine* e, int B, int part = 0) {
-  if (e->persistent) return enqueue_step_persistent(e, B, part);
-  Ctx cx = e->base;
-  cx.B = B;
   if (e->opt_on) cx.fuse_sgd = 0;  // k_reduce writes the gradient only; k_apply_opt applies it
-  if (part == 2) {  // external all-reduce done: averaging SGD + CC4 base
-    if (e->opt_on) return enqueue_apply_opt(e, cx);
-    hipLaunchKernelGGL(e->kapply, dim3(64), dim3(NT), 0, e->st, cx, 1);
-    HIPCK(hipGetLastError());
-    return 0;
-  }
-  const int nparts = B * e->TPI, nw = B * (16 / e->RW);
-  const int nslab = 9 * nw + nparts;
-  const dim3 blk(NT);
-  hipLaunchKernelGGL(e->kstem, dim3(nparts), blk, e->s_stem, e->st, cx);
-  for (int i = 1; i < NBLK; ++i) hipLaunchKernelGGL(e->kfwd, dim3(nparts), blk, e->s_fwd, e->st, cx, i);
-  hipLaunchKernelGGL(e->khead1, dim3(nparts), blk, e->s_head1, e->st, cx);
-  hipLaunchKernelGGL(e->khead2, dim3(nparts), blk, e->s_head2, e->st, cx);
-  for (int i = NBLK - 1; i >= 0; --i) {
-    const int extra = (i == NBLK - 1) ? N_FC_WG : nw;
-    size_t lds = (i == 0) ? e->s_dgrad0 : e->s_dgrad;
-    lds = std::max(lds, (i < NBLK - 1) ? e->s_wgrad : e->s_fc);
-    hipLaunchKernelGGL(e->kbwd, dim3(nparts + extra), blk, lds, e->st, cx, i);
-    if (i == NBLK - 1 && e->comm_on && part == 0 && e->in.comm_mode == 0) {  // bucket A ready: overlap its all-reduce with the trunk bwd
-      HIPCK(hipEventRecord(e->evA, e->st));
-      HIPCK(hipStreamWaitEvent(e->cst, e->evA, 0));
-      NCCK(ncclAllReduce(cx.grads, cx.grads, BUCKET_A_END, ncclFloat32, ncclSum, e->comm, e->cst));
+  if (part != 2) {
+    const dim3 blk(NT), fgrid(p.fwd_grid);
+    hipLaunchKernelGGL(e->kstem, fgrid, blk, p.stem_lds, e->st, cx);
+    for (int i = 1; i < NBLK; ++i) hipLaunchKernelGGL(e->kfwd, fgrid, blk, p.fwd_lds, e->st, cx, i);
+    hipLaunchKernelGGL(e->khead1, fgrid, blk, p.head1_lds, e->st, cx);
+    hipLaunchKernelGGL(e->khead2, fgrid, blk, p.head2_lds, e->st, cx);
+    for (int i = NBLK - 1; i >= 0; --i) {
+      const bool top = i == NBLK - 1;
+      hipLaunchKernelGGL(e->kbwd, dim3(top ? p.bwd9_grid : p.bwd_grid), blk,
+                         top ? p.bwd9_lds : (i ? p.bwd_lds : p.bwd0_lds), e->st, cx, i);
+      if (top && p.overlap_a) {  // bucket A ready: overlap its all-reduce with the trunk bwd
+        HIPCK(hipEventRecord(e->evA, e->st));
+        HIPCK(hipStreamWaitEvent(e->cst, e->evA, 0));
+        NCCK(ncclAllReduce(cx.grads, cx.grads, BUCKET_A_END, ncclFloat32, ncclSum, e->comm, e->cst));
+      }
     }
+    hipLaunchKernelGGL(e->kred, dim3(p.reduce_grid), blk, 0, e->st, cx, p.nslab, p.nparts);
   }
-  const int nother = cx.fuse_sgd ? 64 : 0;
-  hipLaunchKernelGGL(e->kred, dim3(N_TRUNK_RED_WG + N_STEM_RED_WG + nother + 1), blk, 0, e->st, cx, nslab, nparts);
-  if (e->opt_on) {  // the collective on the unapplied gradient, then the optimiser pass in place of kapply
-    if (e->comm_on && part == 0 && e->in.comm_mode == 2) {
-      if (enqueue_xgmi_sum(e, cx)) return -1;
-    } else if (e->comm_on && part == 0) {
-      HIPCK(hipEventRecord(e->evB, e->st));
-      HIPCK(hipStreamWaitEvent(e->cst, e->evB, 0));
-      NCCK(ncclAllReduce(cx.grads + OFF_CONVW, cx.grads + OFF_CONVW, FLAT_N - OFF_CONVW, ncclFloat32, ncclSum, e->comm,
-                         e->cst));
-      HIPCK(hipEventRecord(e->evC, e->cst));
-      HIPCK(hipStreamWaitEvent(e->st, e->evC, 0));
-    }
-    if (part != 1) return enqueue_apply_opt(e, cx);
-    HIPCK(hipGetLastError());
-    return 0;
-  }
-  if (e->comm_on && part == 0 && e->in.comm_mode == 2) return enqueue_xgmi_sgd(e, cx);
-  if (e->comm_on && part == 0) {
-    HIPCK(hipEventRecord(e->evB, e->st));
-    HIPCK(hipStreamWaitEvent(e->cst, e->evB, 0));
-    NCCK(ncclAllReduce(cx.grads + OFF_CONVW, cx.grads + OFF_CONVW, FLAT_N - OFF_CONVW, ncclFloat32, ncclSum, e->comm,
-                       e->cst));
-    HIPCK(hipEventRecord(e->evC, e->cst));
-    HIPCK(hipStreamWaitEvent(e->st, e->evC, 0));
-    hipLaunchKernelGGL(e->kapply, dim3(64), blk, 0, e->st, cx, 1);
-  }
-  HIPCK(hipGetLastError());
-  return 0;
+  return enqueue_tail(e, cx, p.tail);
 }
 
 }  // namespace dca
@@ -500,7 +413,7 @@ extern "C" {
 
 const char* dca_last_error() { return g_err.c_str(); }
 
-int dca_abi_version() { return 9; }  // bump with every DcaInit / signature change
+int dca_abi_version() { return 10; }  // bump with every DcaInit / signature change
 
 int dca_nccl_unique_id(char* out128) {
   ncclUniqueId id;
@@ -530,18 +443,16 @@ static int engine_init(Engine* e, const DcaInit* in, int n_indices) {
   }
   e->TPI = 16 / e->R;
   e->persistent = in->persistent != 0;
-  // comm_on: the step ends with a gradient collective + the averaging SGD kernel.  force_comm runs that path at
-  // world_size 1 (a 1-rank RCCL communicator) so the graph-captured collective is testable on one GPU; loopback
-  // does the same for the xGMI exchange (this rank as its only peer).
   if (in->loopback && (in->world_size != 1 || in->comm_mode != 2)) {
     g_err = "loopback needs world_size 1 and comm_mode 2 (xGMI)";
     return -1;
   }
-  e->comm_on = in->world_size > 1 || (in->force_comm && in->comm_mode == 0) || in->loopback;
+  e->comm_on = dca::comm_on(dca::plan_in(e));
   if (e->bf && e->R == 4) dca::bind_kernels<true, 4, 16>(e);
   else if (e->bf) dca::bind_kernels<true, 2, 16>(e);
   else if (e->R == 4) dca::bind_kernels<false, 4, 8>(e);
   else dca::bind_kernels<false, 2, 8>(e);
+  dca::bind_dtype_kernels(e);
   if (dca::set_lds_limits(e)) return -1;
   if (e->persistent) {
     // Co-residency: the persistent step spins on in-kernel exchanges, so every one of its bmax workgroups must be
@@ -550,26 +461,20 @@ static int engine_init(Engine* e, const DcaInit* in, int n_indices) {
     int dev = 0, ncu = 0, per_cu = 0;
     HIPCK(hipGetDevice(&dev));
     HIPCK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    if (e->bf)
-      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dca::pks::k_pks_step<0>, dca::pks::NTH,
-                                                        dca::pks::Plan<0>::TOTAL));
-    else
-      HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)dca::pks::k_pks_step<1>, dca::pks::NTH,
-                                                        dca::pks::Plan<1>::TOTAL));
+    HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, (const void*)e->kstep, dca::pks::NTH, e->bf ? dca::pks::Plan<0>::TOTAL : dca::pks::Plan<1>::TOTAL));
     // one step workgroup per CU (256 VGPRs): a grid of every CU would leave no slack for anything else on the
     // device (another stream's kernel, another process), so an automatically chosen engine keeps a margin of one
     // workgroup -- batch 64 (256 workgroups) then falls back to the multi-kernel engine with a warning; an
     // explicit persistent=True may use every CU (coresident_budget)
-    const int resident = dca::coresident_budget(per_cu, ncu, 1, !in->auto_engine);
-    const int need = dca::pks_live(in->bmax);
     e->per_cu = per_cu;
     e->ncu = ncu;
-    if (resident < need) {
+    const int need = dca::pks_live(in->bmax);
+    if (dca::share_budget(dca::plan_in(e)) < need) {
       g_err = "persistent engine: " + std::to_string(need) + " workgroups cannot all be resident (" +
               std::to_string(per_cu) + " per CU x " + std::to_string(ncu) + " CUs); use the multi-kernel engine";
       return -1;
     }
-    e->resident = resident;
     if (const char* fo = getenv("DCA_PKS_FC_IN_STEP")) e->fc_in_step = fo[0] != '0';
   }
   HIPCK(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
@@ -602,7 +507,6 @@ static int engine_init(Engine* e, const DcaInit* in, int n_indices) {
   c.indices = e->indices;
   c.n_data = in->n_data;
   c.n_idx = std::max(n_indices, 1);
-  e->peers.ticks = (unsigned long long*)e->regions["COMMT"];
   if ((in->world_size > 1 || in->loopback) && in->comm_mode == 2) {
     if (in->world_size > dca::xg::MAXR) {
       g_err = "xGMI all-reduce: world_size > 8 (one node) -- use RCCL";
@@ -835,34 +739,44 @@ static hipGraphExec_t capture_graph(Engine* e, int B, int chunk) {
   return ex;
 }
 
-int dca_engine_run(void* h, int B, int nsteps, int use_graph) {
-  Engine* e = (Engine*)h;
-  if (B < 1 || B > e->in.bmax) {
+// The argument checks dca_engine_run, _run_checked and _precapture share (external_ok: comm_mode 1 is no error here)
+static int check_run_args(const Engine* e, int B, int nsteps, bool external_ok = false) {
+  if (B < 1 || B > e->in.bmax || nsteps < 0) {
     g_err = "batch out of range";
     return -1;
   }
-  if (e->in.world_size > 1 && e->in.comm_mode == 1) {
+  if (!external_ok && e->in.world_size > 1 && e->in.comm_mode == 1) {
     g_err = "comm_mode 1 (external all-reduce): drive steps with dca_engine_run_part";
     return -1;
   }
+  return 0;
+}
+
+// Graph chunk sizes of `nsteps` steps in launch order: first_chunk-step graphs, then the halves down to 1 (<= 4
+// extra launches for the remainder).  Steps are replayed from graphs holding several consecutive steps (the data
+// cursor / batch ids advance on the device, so consecutive steps need no host input): launching one graph per step
+// leaves a ~5-8 us gap between graph launches on the GPU (rocprofv3, profiles/), inside a graph consecutive kernels
+// are back to back.
+static std::vector<int> chunk_order(int nsteps, int first_chunk) {
+  std::vector<int> order;
+  for (int chunk = first_chunk; chunk >= 1; chunk /= 2)
+    for (; nsteps >= chunk; nsteps -= chunk) order.push_back(chunk);
+  return order;
+}
+
+int dca_engine_run(void* h, int B, int nsteps, int use_graph) {
+  Engine* e = (Engine*)h;
+  if (check_run_args(e, B, 0)) return -1;
   if (nsteps > 0 && ensure_staged(e, B)) return -1;
   if (!use_graph) {
     for (int s = 0; s < nsteps; ++s)
       if (dca::enqueue_step(e, B)) return -1;
     return 0;
   }
-  // Steps are replayed from graphs holding GRAPH_CHUNK consecutive steps (the data cursor / batch ids advance
-  // on the device, so consecutive steps need no host input): launching one graph per step leaves a ~5-8 us
-  // gap between graph launches on the GPU (rocprofv3, profiles/), inside a graph consecutive kernels are
-  // back to back.
-  int done = 0;
-  for (const int chunk : {GRAPH_CHUNK, 8, 4, 2, 1}) {
-    const int reps = (nsteps - done) / chunk;
-    if (reps == 0) continue;
+  for (const int chunk : chunk_order(nsteps, GRAPH_CHUNK)) {
     hipGraphExec_t ex = capture_graph(e, B, chunk);
     if (ex == nullptr) return -1;
-    for (int r = 0; r < reps; ++r) HIPCK(hipGraphLaunch(ex, e->st));
-    done += reps * chunk;
+    HIPCK(hipGraphLaunch(ex, e->st));
   }
   return 0;
 }
@@ -879,19 +793,10 @@ int dca_engine_run_checked(void* h, int B, int nsteps, int* steps_done) {
   Engine* e = (Engine*)h;
   constexpr int RING = 4;
   *steps_done = 0;
-  if (B < 1 || B > e->in.bmax || nsteps < 0) {
-    g_err = "batch out of range";
-    return -1;
-  }
-  if (e->in.world_size > 1 && e->in.comm_mode == 1) {
-    g_err = "comm_mode 1 (external all-reduce): drive steps with dca_engine_run_part";
-    return -1;
-  }
+  if (check_run_args(e, B, nsteps)) return -1;
   if (nsteps > 0 && ensure_staged(e, B)) return -1;
-  int left = nsteps;
-  std::vector<int> order;  // graph chunk sizes in launch order (16s, then 8 / 4 / 2 / 1)
-  for (const int chunk : {8, 4, 2, 1})  // 8-step chunks: a failure is seen within < 16 steps (2 chunks in flight)
-    for (; left >= chunk; left -= chunk) order.push_back(chunk);
+  // 8-step chunks: a failure is seen within < 16 steps (2 chunks in flight)
+  const std::vector<int> order = chunk_order(nsteps, 8);
   int launched = 0, rc = 0;
   size_t k = 0, checked = 0;
   auto check = [&](size_t j) -> int {  // chunk j's words (its event first)
@@ -930,12 +835,9 @@ int dca_engine_run_checked(void* h, int B, int nsteps, int* steps_done) {
 // capture + instantiate.  Synchronous.
 int dca_engine_precapture(void* h, int B) {
   Engine* e = (Engine*)h;
-  if (B < 1 || B > e->in.bmax) {
-    g_err = "batch out of range";
-    return -1;
-  }
+  if (check_run_args(e, B, 0, true)) return -1;
   if (e->in.world_size > 1 && e->in.comm_mode == 1) return 0;  // external all-reduce: eager only
-  for (const int chunk : {GRAPH_CHUNK, 8, 4, 2, 1})
+  for (const int chunk : chunk_order(2 * GRAPH_CHUNK - 1, GRAPH_CHUNK))  // one graph of each size: 16, 8, 4, 2, 1
     if (capture_graph(e, B, chunk) == nullptr) return -1;
   HIPCK(hipStreamSynchronize(e->st));
   return 0;
@@ -1002,24 +904,11 @@ int dca_engine_ipc_selftest(void* h, const float* src, float* dst, float timeout
   HIPCK(hipMemsetAsync(e->qa.err + 1, 0, sizeof(unsigned), e->st));
   const unsigned long long dl = (unsigned long long)((double)timeout_s * 1e8);
   if (e->persistent) {  // the path a sliced training step uses: per-segment exchange inside the fused reduce kernel
-    dca::pks::RedAr ra = dca::red_args(e, 3, 0, dl);  // (flags 0: every segment in the reduction kernel)
-    ra.peers.ticks = nullptr;
-    ra.st_src = src;
-    ra.st_dst = dst;
-    ra.st_n = dca::FLAT_N;
-    dca::Ctx cx = e->base;
-    cx.B = 1;
-    hipLaunchKernelGGL(dca::pks::k_pks_reduce_ar<0>, dim3(dca::reduce_grid(e, dca::pks::seg_layout(ra.seg_ch).nseg)),
-                       dim3(256), dca::pks::stage_floats(1) * 4, e->st, cx, e->qa, 1, ra);
+    dca::launch_selftest_reduce(e, dca::selftest_redar(e, src, dst, 0, dl));  // (flags 0: every segment)
   } else {
     dca::xg::Peers P = e->peers;
     P.ticks = nullptr;  // a self-test is not training-step communication (metrics)
-    if (e->bf)
-      hipLaunchKernelGGL(dca::xg::k_xgmi_ar_sgd<true>, dim3(dca::xg::AR_NB), dim3(dca::xg::AR_T), 0, e->st,
-                         e->base, P, src, dst, e->qa.err + 1, 0, dl);
-    else
-      hipLaunchKernelGGL(dca::xg::k_xgmi_ar_sgd<false>, dim3(dca::xg::AR_NB), dim3(dca::xg::AR_T), 0, e->st,
-                         e->base, P, src, dst, e->qa.err + 1, 0, dl);
+    dca::launch_xgmi(e, e->base, P, src, dst, 0, dl);
   }
   HIPCK(hipGetLastError());
   HIPCK(hipStreamSynchronize(e->st));
@@ -1043,22 +932,14 @@ int dca_engine_ipc_selftest_fc(void* h, const float* src, float* dst, float time
     return -1;
   }
   HIPCK(hipMemsetAsync(e->qa.err, 0, 2 * sizeof(unsigned), e->st));
-  dca::pks::RedAr ra = dca::red_args(e, 3, 1, (unsigned long long)((double)timeout_s * 1e8));
-  ra.peers.ticks = nullptr;
-  ra.st_src = src;
-  ra.st_dst = dst;
-  ra.st_n = dca::FLAT_N;
+  const dca::pks::RedAr ra = dca::selftest_redar(e, src, dst, 1, (unsigned long long)((double)timeout_s * 1e8));
   dca::Ctx cx = e->base;
   cx.B = 0;  // no step workgroups: the whole grid is fc workers
   // one workgroup per fc segment, or (ranks sharing the device) the rank's CU budget: every rank's workgroup f waits
   // for its peers' workgroup f, so all ranks' grids must be co-resident (a step-kernel workgroup takes a whole CU)
-  const dim3 grid(std::min(dca::pks::N_FCW, dca::share_budget(e)));
-  if (e->bf)
-    hipLaunchKernelGGL((dca::pks::k_pks_step<0>), grid, dim3(dca::pks::NTH), dca::pks::Plan<0>::TOTAL, e->st, cx, e->qa,
-                       ra);
-  else
-    hipLaunchKernelGGL((dca::pks::k_pks_step<1>), grid, dim3(dca::pks::NTH), dca::pks::Plan<1>::TOTAL, e->st, cx, e->qa,
-                       ra);
+  const dim3 grid(std::min(dca::pks::N_FCW, dca::share_budget(dca::plan_in(e))));
+  hipLaunchKernelGGL(e->kstep, grid, dim3(dca::pks::NTH), e->bf ? dca::pks::Plan<0>::TOTAL : dca::pks::Plan<1>::TOTAL,
+                     e->st, cx, e->qa, ra);
   HIPCK(hipGetLastError());
   HIPCK(hipStreamSynchronize(e->st));
   unsigned f[2] = {0, 0};
@@ -1085,24 +966,11 @@ int dca_engine_ipc_bench(void* h, const float* src, float* dst, int iters, float
   HIPCK(hipEventRecord(a, e->st));
   dca::xg::Peers P = e->peers;
   P.ticks = nullptr;  // benchmark traffic stays out of the training comm-time counters
+  // sliced engine: the exchange a sliced training step runs: every gradient segment, self-test mode
+  const dca::pks::RedAr ra = dca::selftest_redar(e, src, dst, 0, e->ar_deadline);
   for (int i = 0; i < iters; ++i) {
-    if (e->persistent) {  // the exchange a sliced training step runs: every gradient segment, self-test mode
-      dca::pks::RedAr ra = dca::red_args(e, 3, 0, e->ar_deadline);
-      ra.peers = P;
-      ra.st_src = src;
-      ra.st_dst = dst;
-      ra.st_n = dca::FLAT_N;
-      dca::Ctx cx = e->base;
-      cx.B = 1;
-      hipLaunchKernelGGL(dca::pks::k_pks_reduce_ar<0>, dim3(dca::reduce_grid(e, dca::pks::seg_layout(ra.seg_ch).nseg)),
-                         dim3(256), dca::pks::stage_floats(1) * 4, e->st, cx, e->qa, 1, ra);
-    } else if (e->bf) {
-      hipLaunchKernelGGL(dca::xg::k_xgmi_ar_sgd<true>, dim3(dca::xg::AR_NB), dim3(dca::xg::AR_T), 0, e->st,
-                         e->base, P, src, dst, e->qa.err + 1, 0, e->ar_deadline);
-    } else {
-      hipLaunchKernelGGL(dca::xg::k_xgmi_ar_sgd<false>, dim3(dca::xg::AR_NB), dim3(dca::xg::AR_T), 0, e->st,
-                         e->base, P, src, dst, e->qa.err + 1, 0, e->ar_deadline);
-    }
+    if (e->persistent) dca::launch_selftest_reduce(e, ra);
+    else dca::launch_xgmi(e, e->base, P, src, dst, 0, e->ar_deadline);
   }
   HIPCK(hipEventRecord(b, e->st));
   HIPCK(hipEventSynchronize(b));
@@ -1114,7 +982,7 @@ int dca_engine_ipc_bench(void* h, const float* src, float* dst, int iters, float
   return 0;
 }
 
-// comm_mode 1: one part of a step, eager (see enqueue_step_persistent)
+// comm_mode 1: one part of a step, eager (see engine_plan)
 int dca_engine_run_part(void* h, int B, int part) {
   Engine* e = (Engine*)h;
   if (B < 1 || B > e->in.bmax || part < 1 || part > 2 || e->in.world_size < 2 || e->in.comm_mode != 1) {
@@ -1130,6 +998,12 @@ int dca_engine_sync(void* h) {
   HIPCK(hipStreamSynchronize(e->st));
   HIPCK(hipStreamSynchronize(e->cst));
   return 0;
+}
+
+// Drop the captured step graphs (the step's kernel chain is about to change).  The stream must be idle.
+static void drop_graphs(Engine* e) {
+  for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
+  e->graphs.clear();
 }
 
 // Sliced engine: the host reports that `n` xGMI ranks share this device (shared-GPU rehearsal; the largest such
@@ -1149,16 +1023,9 @@ int dca_engine_set_shared_device(void* h, int n) {
     }
   }
   HIPCK(hipStreamSynchronize(e->st));
-  for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-  e->graphs.clear();
+  drop_graphs(e);
   e->shared_device = n > 1 ? n : 0;
   return 0;
-}
-
-// Drop the captured step graphs (the step's kernel chain is about to change).  The stream must be idle.
-static void drop_graphs(Engine* e) {
-  for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-  e->graphs.clear();
 }
 
 // Optimiser of the fused step: SGD with momentum `mu` and weight decay `wd` (optimizer.hip).  `momentum_buf`: flat
@@ -1261,8 +1128,17 @@ int dca_engine_opt_step(void* h, int set, int* value) {
 // Sliced engine: 1 if a step at batch B runs the fc gradient segments on the step kernel's fc workers.
 int dca_engine_fc_in_step(void* h, int B) {
   Engine* e = (Engine*)h;
-  return e->persistent && fc_in_step_for(e, B) ? 1 : 0;
+  return e->persistent && dca::fc_in_step_for(dca::plan_in(e), B) ? 1 : 0;
 }
+
+// The step plan (engine_plan.h) of any configuration: needs no engine and no device.  0, or -1 with the reason the
+// step cannot run in dca_last_error.
+int dca_engine_step_plan(const PlanIn* in, int B, int part, StepPlan* out) {
+  return dca::plan_step(*in, B, part, out);
+}
+
+// What the step plan reads of this engine: dca_engine_step_plan(out, B, part, ..) is the plan of its next step.
+void dca_engine_plan_in(void* h, PlanIn* out) { *out = dca::plan_in((Engine*)h); }
 
 
 // Handle of the engine stream (so Python can order torch work against it).
@@ -1271,8 +1147,9 @@ void* dca_engine_stream(void* h) { return ((Engine*)h)->st; }
 // Device pointer of a named workspace region (tests / debugging).
 void* dca_engine_region(void* h, const char* name) {
   Engine* e = (Engine*)h;
-  auto it = e->regions.find(name);
-  return it == e->regions.end() ? nullptr : it->second;
+  for (const auto& r : e->regions)
+    if (!strcmp(r.name, name)) return r.ptr;
+  return nullptr;
 }
 
 size_t dca_engine_workspace_bytes(void* h) { return ((Engine*)h)->ws_bytes; }

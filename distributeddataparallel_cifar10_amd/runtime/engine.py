@@ -113,7 +113,7 @@ S_SLICES = 4  # workgroups per image of the sliced step (csrc/netresdeep_pks.hip
 
 
 def coresident_budget(per_cu: int, ncu: int, n_share: int = 1, full_device: bool = False) -> int:
-    """Spinning workgroups ONE rank may hold resident at once (csrc/engine.hip coresident_budget, same rule): the
+    """Spinning workgroups ONE rank may hold resident at once (csrc/engine_plan.h coresident_budget, same rule): the
     device's slots minus a margin -- one block per CU when several fit, else one CU (none only when a dedicated
     device was asked for explicitly) -- split evenly over the ranks sharing the device."""
     slots = per_cu * ncu
@@ -353,6 +353,14 @@ class NetResDeepEngine:
     def fc_in_step(self, batch: int) -> bool:
         """Whether a step at this batch size runs the fc gradient segments on the step kernel's fc workers."""
         return bool(self.lib.dca_engine_fc_in_step(self.h, int(batch)))
+
+    def step_plan(self, batch: int, part: int = 0) -> "native.StepPlan":
+        """What this engine's next step at this batch size launches (csrc/engine_plan.h; pure, nothing is enqueued)."""
+        pin, plan = native.PlanIn(), native.StepPlan()
+        self.lib.dca_engine_plan_in(self.h, ctypes.byref(pin))
+        native.check(self.lib.dca_engine_step_plan(ctypes.byref(pin), int(batch), int(part), ctypes.byref(plan)),
+                     "dca_engine_step_plan")
+        return plan
 
     # ---- state sync ---------------------------------------------------------------------------------------
     def derive(self):

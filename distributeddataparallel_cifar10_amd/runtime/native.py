@@ -16,13 +16,33 @@ import torch  # noqa: F401  (must be imported before the native library, see mod
 
 from .. import build as _build
 
-ABI_VERSION = 9  # csrc/engine.hip dca_abi_version(): DcaInit layout / C signatures
+ABI_VERSION = 10  # csrc/engine.hip dca_abi_version(): DcaInit layout / C signatures
 _lock = threading.Lock()
 _lib = None
 
 
 class NativeUnavailable(RuntimeError):
     pass
+
+
+class PlanIn(ctypes.Structure):
+    """csrc/engine_plan.h PlanIn, field by field: what the step plan depends on."""
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "persistent", "bf16", "rows", "world_size", "comm_mode", "force_comm", "loopback", "opt_on", "shared_device",
+        "fc_in_step", "per_cu", "ncu", "full_device", "bmax")]
+
+
+class StepPlan(ctypes.Structure):
+    """csrc/engine_plan.h StepPlan, field by field: what one step launches."""
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "tail", "reduce_grid",
+        "budget", "step_grid", "step_block", "step_lds", "fc", "mode", "seg_ch", "reduce_form", "reduce_lds",
+        "nparts", "nslab", "fwd_grid", "bwd9_grid", "bwd_grid", "stem_lds", "fwd_lds", "head1_lds", "head2_lds",
+        "bwd9_lds", "bwd_lds", "bwd0_lds", "overlap_a")]
+
+
+# csrc/engine_plan.h StepTail: what follows the gradient reduction
+TAIL_NONE, TAIL_RCCL_SGD, TAIL_SGD, TAIL_XGMI_OPT, TAIL_RCCL_OPT, TAIL_OPT, TAIL_XGMI_SGD = range(7)
 
 
 def _declare(lib):
@@ -59,6 +79,9 @@ def _declare(lib):
     lib.dca_engine_set_epoch.argtypes = [c_void_p, c_int, c_int]
     lib.dca_engine_epoch.argtypes = [c_void_p, ctypes.POINTER(c_int)]
     lib.dca_engine_fc_in_step.argtypes = [c_void_p, c_int]
+    lib.dca_engine_step_plan.argtypes = [ctypes.POINTER(PlanIn), c_int, c_int, ctypes.POINTER(StepPlan)]
+    lib.dca_engine_plan_in.argtypes = [c_void_p, ctypes.POINTER(PlanIn)]
+    lib.dca_engine_plan_in.restype = None
     lib.dca_engine_set_optimizer.argtypes = [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float]
     lib.dca_engine_set_lr_table.argtypes = [c_void_p, c_void_p, c_int]
     lib.dca_engine_opt_step.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]

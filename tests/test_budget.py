@@ -1,4 +1,4 @@
-"""The co-residency rule of the sliced engine (csrc/engine.hip coresident_budget, mirrored in runtime/engine.py): one
+"""The co-residency rule of the sliced engine (csrc/engine_plan.h coresident_budget, mirrored in runtime/engine.py): one
 rule for a device of its own and a device shared by n ranks.  CPU-only (pure arithmetic); the GPU tier checks that
 the native rule refuses the same configurations (tests/test_engine_gpu.py::test_shared_device_budget_refuses_exact_fill).
 """
@@ -39,7 +39,7 @@ def test_several_blocks_per_cu_keep_one_per_cu():
 def test_native_rule_is_the_same_formula():
     """The C++ function must keep the same margin expression (a drift would let the two disagree silently)."""
     src = open(os.path.join(os.path.dirname(__file__), "..", "distributeddataparallel_cifar10_amd", "csrc",
-                            "engine.hip")).read()
+                            "engine_plan.h")).read()
     body = re.search(r"static int coresident_budget\(.*?\n}", src, re.S).group(0)
     assert "per_cu > 1 ? ncu : (full_device && n_share <= 1 ? 0 : 1)" in body
     assert "(slots - margin) / std::max(n_share, 1)" in body

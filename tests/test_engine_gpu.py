@@ -100,7 +100,7 @@ def test_trajectory_across_epoch_wrap(gpu, dtype, tol):
 
 
 def test_shared_device_budget_refuses_exact_fill(gpu):
-    """One co-residency rule (csrc/engine.hip coresident_budget, mirrored by runtime/engine.py): 8 ranks sharing the
+    """One co-residency rule (csrc/engine_plan.h coresident_budget, mirrored by runtime/engine.py): 8 ranks sharing the
     device at batch_max 8 (8 x 32 live step workgroups = every CU) are refused when the sharing is declared --
     before any step could spin in a BN exchange that cannot complete -- while batch_max 4 is accepted."""
     from distributeddataparallel_cifar10_amd.data.synthetic import synthetic_cifar

@@ -128,7 +128,7 @@ def test_native_eval_entry_validates_before_any_launch():
     """dca_eval_netresdeep checks its arguments on the host, before any device call: on a machine without a GPU a bad
     call returns -1 with a message (a launch attempt would fail with a HIP error instead)."""
     lib = native.load()
-    assert lib.dca_abi_version() == native.ABI_VERSION == 9
+    assert lib.dca_abi_version() == native.ABI_VERSION == 10
     assert hasattr(lib, "dca_eval_netresdeep")
     buf = (ctypes.c_char * 4096)()
     p = ctypes.addressof(buf)

@@ -81,6 +81,108 @@ def test_code_object_targets_gfx950():
     assert b"amdgcn-amd-amdhsa--gfx950" in blob
 
 
+def _engine_lib():
+    from distributeddataparallel_cifar10_amd.runtime import native
+    return native._declare(ctypes.CDLL(nbuild.build(), mode=ctypes.RTLD_GLOBAL)), native
+
+
+def _step_plan(lib, native, B, part=0, **over):
+    """The plan on an MI355X (256 CUs, one step workgroup per CU), bf16, world size 1, no optimiser, sliced engine,
+    automatic choice -- unless overridden."""
+    pin = native.PlanIn(persistent=1, bf16=1, rows=4, world_size=1, fc_in_step=1, per_cu=1, ncu=256, bmax=64)
+    for k, v in over.items():
+        setattr(pin, k, v)
+    plan = native.StepPlan()
+    rc = lib.dca_engine_step_plan(ctypes.byref(pin), B, part, ctypes.byref(plan))
+    return rc, plan
+
+
+# dca_engine_step_plan, written by hand from the rule's comments in csrc/engine_plan.h (and csrc/netresdeep_pks.hip
+# seg_layout: 128-element chunks give 72 trunk + 9 conv1 segments, 256-element ones 36 + 5; + 64 fc1 blocks + fc tail
+# + BN tail).  (batch, part, overrides) -> expected fields.
+_XGMI2 = dict(world_size=2, comm_mode=2, shared_device=2)
+_RCCL2 = dict(world_size=2, comm_mode=0)
+_STEP_PLANS = [
+    # automatic choice: one CU kept free; 128 step workgroups + 65 fc workers; 81 trunk / conv1 segments + BN tail
+    # + bookkeeping in the lean world-size-1 reduction; 96 staging floats per image
+    (32, 0, {}, dict(budget=255, fc=1, step_grid=193, step_block=512, step_lds=138528, mode=0, seg_ch=128,
+                     reduce_form=1, reduce_grid=83, reduce_lds=12288, tail=0)),
+    (3, 0, {}, dict(step_grid=97, fc=1, reduce_lds=1152)),          # image slots rounded up to 8: 32 + 65
+    (32, 0, dict(bf16=0), dict(step_grid=193, step_lds=152384)),
+    # the whole device: 256 + 65 > 256, so every one of the 147 segments (+ 1) runs in the general reduction
+    (64, 0, dict(full_device=1), dict(budget=256, fc=0, step_grid=256, reduce_form=0, reduce_grid=148)),
+    # two xGMI ranks on one device: half of 255 each, the coarse layout, 41 + 1 + 1 reduction workgroups
+    (8, 0, _XGMI2, dict(budget=127, seg_ch=256, fc=1, step_grid=97, mode=2, reduce_form=2, reduce_grid=43, tail=0)),
+    # eight: 31 each; 16 + 65 > 31; the 107 + 1 reduction workgroups capped at the budget
+    (4, 0, dict(world_size=8, comm_mode=2, shared_device=8, bmax=4),
+     dict(budget=31, fc=0, step_grid=32, mode=2, reduce_form=0, reduce_grid=31, tail=0)),
+    # RCCL: gradient only (the general reduction), then the collective and k_apply_sgd
+    (32, 0, _RCCL2, dict(mode=1, fc=1, reduce_form=0, reduce_grid=83, tail=1)),
+    (32, 0, dict(force_comm=1), dict(mode=1, reduce_form=0, tail=1)),
+    # the host all-reduces between parts 1 and 2
+    (32, 1, dict(world_size=2, comm_mode=1), dict(mode=1, step_grid=193, reduce_grid=83, tail=0)),
+    (32, 2, dict(world_size=2, comm_mode=1), dict(step_grid=0, reduce_grid=0, tail=2)),
+    # optimiser pass: gradient only, whatever the world size
+    (32, 0, dict(opt_on=1), dict(mode=1, reduce_form=0, tail=5)),
+    (8, 0, dict(_XGMI2, opt_on=1), dict(mode=1, reduce_form=0, tail=3)),
+    (32, 0, dict(_RCCL2, opt_on=1), dict(mode=1, tail=4)),
+    (32, 2, dict(world_size=2, comm_mode=1, opt_on=1), dict(step_grid=0, tail=5)),
+    (32, 0, dict(world_size=1, comm_mode=2, loopback=1), dict(mode=2, reduce_form=2, tail=0)),
+    # DCA_PKS_FC_IN_STEP=0
+    (32, 0, dict(fc_in_step=0), dict(fc=0, step_grid=128, reduce_form=0, reduce_grid=148)),
+    # multi-kernel engine, rows 4 (4 tiles per image), bf16 (one weight-gradient workgroup per image): block 9's
+    # backward carries the 32 fc workgroups, the others the 64 weight-gradient ones; 9 x 64 + 256 slabs; k_reduce with
+    # 288 trunk + 34 stem + 64 other (it applies the SGD itself) + 1
+    (64, 0, dict(persistent=0), dict(nparts=256, fwd_grid=256, bwd9_grid=288, bwd_grid=320, nslab=832,
+                                     reduce_grid=387, overlap_a=0, tail=0)),
+    (64, 0, dict(persistent=0, **_RCCL2), dict(nparts=256, reduce_grid=323, overlap_a=1, tail=1)),
+    (64, 0, dict(persistent=0, world_size=2, comm_mode=2), dict(reduce_grid=323, overlap_a=0, tail=6)),
+    (64, 0, dict(persistent=0, opt_on=1), dict(reduce_grid=323, tail=5)),
+    (64, 0, dict(persistent=0, opt_on=1, **_RCCL2), dict(overlap_a=1, tail=4)),
+    # fp32: 8-row weight-gradient tiles, two per image; rows 2: 8 tiles per image
+    (3, 0, dict(persistent=0, bf16=0, rows=2), dict(nparts=24, bwd9_grid=56, bwd_grid=30, nslab=78)),
+]
+
+
+def test_step_plans_match_table():
+    """dca_engine_step_plan (csrc/engine_plan.h, no device and no engine needed) against the hand-written table above,
+    the refusals, and the Python mirror of the budget."""
+    lib, native = _engine_lib()
+    assert lib.dca_abi_version() == native.ABI_VERSION
+    src = open(os.path.join(nbuild.CSRC, "engine_plan.h")).read()
+    for cls in (native.PlanIn, native.StepPlan):  # the ctypes mirrors list the header's fields in the same order
+        body = src[src.index("struct %s {" % cls.__name__):]
+        body = body[:body.index("};")]
+        decl = [n.strip() for line in body.splitlines()[1:] if line.split("//")[0].strip()
+                for n in line.split("//")[0].strip().rstrip(";").replace("int ", "").split(",")]
+        assert decl == [f[0] for f in cls._fields_], cls.__name__
+    assert "TAIL_NONE = 0" in src and "TAIL_RCCL_SGD = 1" in src and "TAIL_SGD = 2" in src and \
+        "TAIL_XGMI_OPT = 3" in src and "TAIL_RCCL_OPT = 4" in src and "TAIL_OPT = 5" in src and "TAIL_XGMI_SGD = 6" in src
+    assert (native.TAIL_NONE, native.TAIL_RCCL_SGD, native.TAIL_SGD, native.TAIL_XGMI_OPT, native.TAIL_RCCL_OPT,
+            native.TAIL_OPT, native.TAIL_XGMI_SGD) == tuple(range(7))
+    bad = []
+    for B, part, over, want in _STEP_PLANS:
+        rc, plan = _step_plan(lib, native, B, part, **over)
+        got = {k: getattr(plan, k) for k in want}
+        if rc != 0 or got != want:
+            bad.append((B, part, over, rc, got, want))
+    assert not bad, bad
+    # refusals: the automatic choice cannot hold batch 64 (256 live workgroups > 255); batches outside [1, bmax];
+    # parts 1 / 2 without the external all-reduce
+    rc, _ = _step_plan(lib, native, 64)
+    assert rc == -1 and lib.dca_last_error() == (b"persistent engine: 256 step workgroups (batch 64) exceed the "
+                                                 b"co-residency budget of 255 per rank")
+    for B, over in ((0, {}), (33, dict(bmax=32)), (65, dict(full_device=1))):
+        assert _step_plan(lib, native, B, **over)[0] == -1 and lib.dca_last_error() == b"batch out of range"
+    assert _step_plan(lib, native, 32, 1)[0] == -1 and _step_plan(lib, native, 32, 3, world_size=2, comm_mode=1)[0] == -1
+    for per_cu in (1, 2):
+        for share in (1, 2, 4, 8):
+            for full in (0, 1):
+                rc, plan = _step_plan(lib, native, 1, per_cu=per_cu, shared_device=share, full_device=full,
+                                      world_size=share, comm_mode=2 if share > 1 else 0)
+                assert rc == 0 and plan.budget == E.coresident_budget(per_cu, 256, share, bool(full)), (per_cu, share)
+
+
 def test_ops_library_builds_and_exports():
     """The ops layer's library (csrc/ops_api.hip) cross-compiles for gfx950 and exports its C ABI."""
     path = nbuild.build(variant="ops")

@@ -89,8 +89,8 @@ def main():
     n = 256
     eye = torch.eye(n, device=dev, dtype=bf)
     bi = torch.arange(128 * n, device=dev).remainder(61).float().view(128, n).to(bf)  # B [N = 128, K = n]
-    y = ops.gemm(eye, bi, out_dtype=bf)  # C[m, c] = B[c, m]
-    assert last_gemm_kernel() == "k_gemm_glds<false, 128, 4>", last_gemm_kernel()  # (ops.gemm splits K = 256 in two)
+    y = ops.gemm(eye, bi, out_dtype=bf, splits=1)  # C[m, c] = B[c, m]  (splits=0 would split K = 256 in two)
+    assert last_gemm_kernel() == "k_gemm_stream<2, 1, false>", last_gemm_kernel()
     out["identity_exact_err"] = float((y.float() - bi.float().t()).abs().max())
     print(json.dumps(out), flush=True)
 

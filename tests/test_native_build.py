@@ -272,6 +272,38 @@ def test_gemm_routes_match_golden():
     assert len(ids) == 49 and sorted(ids.values()) == list(range(49))  # every instantiation keeps a route
 
 
+def test_gemm_form_cases_cover_the_table():
+    """tests/_gemm_forms.py, the case table of tests/test_ops_gemm_forms_gpu.py, with no device: the GemmArgs the GPU
+    test passes for every case and form (same shape fields, same null / non-null pointers, every base 16-B aligned)
+    route to the kernel the case claims, with the claimed splits / reduce / masked copy; and the claimed names plus
+    EXCLUDED are exactly the 49 instantiations of tests/golden/gemm_routes.json, so an instantiation no case runs
+    fails here."""
+    import json
+    import _gemm_forms as GF
+    lib, _native = _ops_lib()
+    bad, claimed = [], set()
+    assert len({c.id for c in GF.CASES}) == len(GF.CASES)
+    for c in GF.CASES:
+        assert len({f.name for f in c.forms}) == len(c.forms) > 0, c.id
+        for f in c.forms:
+            rc, r = _route(lib, _native, GF.gemm_fields(c, f))
+            if rc != 0:
+                bad.append((c.id, f.name, lib.dca_ops_last_error().decode()))
+                continue
+            want = GF.claims(c, f)
+            got = {k: r.name.decode() if k == "name" else getattr(r, k) for k in want}
+            if got != want:
+                bad.append((c.id, f.name, got, want))
+            claimed.add(want["name"])
+    assert not bad, bad[:10]
+    golden = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "gemm_routes.json")))
+    names = {g["route"]["name"] for g in golden}
+    assert len(names) == 49
+    assert not claimed & set(GF.EXCLUDED), claimed & set(GF.EXCLUDED)
+    assert claimed | set(GF.EXCLUDED) == names, (names - claimed - set(GF.EXCLUDED), (claimed | set(GF.EXCLUDED)) - names)
+    assert all(isinstance(v, str) and len(v) > 20 for v in GF.EXCLUDED.values())
+
+
 def test_gemm_route_rejects_bad_shapes():
     """One shape per class of check that integers alone reach: -1 and a message, with no device and no launch."""
     lib, _native = _ops_lib()

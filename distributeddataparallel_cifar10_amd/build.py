@@ -1,8 +1,9 @@
 """Build the native HIP/C++ code of the framework for gfx950 (MI355X), in-tree.
 
 ``python -m distributeddataparallel_cifar10_amd.build`` compiles, with ``hipcc --offload-arch=gfx950``:
-  * ``csrc/engine.hip`` (the NetResDeep training engine + xGMI all-reduce) and ``csrc/optimizer.hip`` (the engine's
-    optimiser pass, a translation unit and code object of its own) -> ``_lib/libdca_engine.so``
+  * ``csrc/engine.hip`` (the NetResDeep training engine + xGMI all-reduce), ``csrc/optimizer.hip`` (the engine's
+    optimiser pass) and ``csrc/augment.hip`` (the crop + flip pass over the uint8 dataset), each a translation unit
+    and code object of its own -> ``_lib/libdca_engine.so``
   * ``csrc/ops_api.hip`` (the general layer kernels of ``ops/``: MFMA GEMM bf16/fp8, im2col, BN, pooling, CE,
     SGD, fp8 quantisation) -> ``_lib/libdca_ops.so``
   * ``csrc/comm_api.hip`` (generic xGMI one-shot / two-shot all-reduce for any model's flat buckets)
@@ -31,7 +32,7 @@ MICRO_LIB = os.path.join(LIB_DIR, "libdca_micro.so")
 _ENTRY = {"ops": ("ops_api.hip", OPS_LIB), "comm": ("comm_api.hip", COMM_LIB),
           # calibration micro-benchmarks (bench/micro): diagnostic, never loaded by the framework itself
           "micro": (os.path.join(os.path.dirname(PKG_DIR), "bench", "micro", "engine_micro.hip"), MICRO_LIB)}
-ENGINE_SOURCES = ("engine.hip", "optimizer.hip")  # translation units of the engine library (and its variants)
+ENGINE_SOURCES = ("engine.hip", "optimizer.hip", "augment.hip")  # translation units of the engine library (and variants)
 ARCH = os.environ.get("DCA_OFFLOAD_ARCH", "gfx950")
 # Variants: "" = production; "stamps" = diagnostic build with in-kernel phase stamps (-DDCA_STAMPS).
 VARIANTS = {"": [], "stamps": ["-DDCA_STAMPS"], "ops": [], "comm": [], "micro": []}

@@ -9,6 +9,10 @@ Here the uint8 dataset (150 MB for CIFAR-10) is uploaded to HBM once.  An epoch 
 (``data/sampler.py``); the fused engine gathers + normalises a batch inside its stem kernel, and the generic torch
 path (``__iter__``) gathers + normalises on the device.  ``len(loader)`` equals the reference DataLoader's length
 (ragged last batch kept), which is what the printed mean loss divides by (``main.py:44``).
+
+``augment=AugmentConfig(...)`` (off by default; an extension, the reference has no augmentation) keeps a second
+dataset tensor whose rows one pass per epoch rewrites with a random crop + flip of the pristine rows
+(``data/augment.py``); without it nothing is allocated and nothing runs.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ from typing import Iterator, Optional, Tuple
 import numpy as np
 import torch
 
+from .augment import IMAGE_SHAPE, AugmentConfig, augment_u8
 from .cifar import normalize_u8
 from .sampler import batches_per_epoch, distributed_indices
 
@@ -24,11 +29,20 @@ from .sampler import batches_per_epoch, distributed_indices
 class DeviceLoader:
     def __init__(self, data_u8: torch.Tensor, labels: torch.Tensor, batch_size: int = 32, world_size: int = 1,
                  rank: int = 0, device=None, sampler: str = "distributed", seed: Optional[int] = 0, drop_last: bool = False,
-                 set_epoch: bool = False):
+                 set_epoch: bool = False, augment: Optional[AugmentConfig] = None):
         if sampler not in ("distributed", "random", "sequential"):
             raise ValueError("sampler must be 'distributed', 'random' or 'sequential'")
         device = torch.device(device) if device is not None else data_u8.device
         self.data = data_u8.to(device).contiguous()
+        self.augment = augment
+        if augment is not None:
+            # `source` stays pristine; `data` (what the engines and __iter__ read, at a fixed address for the whole
+            # run: the engines capture it in their graphs) is rewritten row by row, once per epoch
+            if self.data.dtype != torch.uint8 or tuple(self.data.shape[1:]) != IMAGE_SHAPE:
+                raise ValueError("augmentation needs a uint8 [N, 3, 32, 32] dataset, got "
+                                 f"{self.data.dtype} {tuple(self.data.shape)}")
+            self.source = self.data
+            self.data = self.source.clone()
         self.labels = labels.to(device=device, dtype=torch.int64).contiguous()
         self.batch_size = int(batch_size)
         self.world_size, self.rank = int(world_size), int(rank)
@@ -61,8 +75,19 @@ class DeviceLoader:
                                           drop_last=self.drop_last)) if self.sampler == "distributed" else self.n
         return batches_per_epoch(n_local, self.batch_size, self.drop_last)
 
+    def augment_epoch(self, ids=None, stream=None) -> None:
+        """With an ``AugmentConfig``: rewrite the rows `ids` (None: every row) of ``data`` from ``source`` with the
+        current epoch's draw (``data/augment.py``), on `stream` (None: torch's current stream; a torch stream; a raw
+        ``hipStream_t``).  Without one: nothing."""
+        if self.augment is None:
+            return
+        a = self.augment
+        augment_u8(self.source, self.data, ids, seed=a.seed, epoch=self.epoch, pad=a.pad, flip=a.flip, stream=stream)
+
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
-        idx = torch.from_numpy(self.indices()).to(self.device)
+        order = self.indices()  # once: the "random" sampler draws a new permutation on every call
+        self.augment_epoch(order)
+        idx = torch.from_numpy(order).to(self.device)
         for s in range(0, len(idx), self.batch_size):
             b = idx[s:s + self.batch_size]
             if self.drop_last and len(b) < self.batch_size:

@@ -48,7 +48,10 @@ class FusedDDPTrainer:
     def __init__(self, model: nn.Module, data_u8: torch.Tensor, labels: torch.Tensor, batch_max: int = 32,
                  lr: float = 1e-2, dtype: str = "bf16", rows: int = 4, max_indices: Optional[int] = None,
                  persistent: Optional[bool] = None, comm: str = "auto", loopback: bool = False,
-                 full_device: bool = False, optimizer: Optional[OptimizerConfig] = None):
+                 full_device: bool = False, optimizer: Optional[OptimizerConfig] = None,
+                 eval_data: Optional[torch.Tensor] = None):
+        """`eval_data`: the dataset ``engine.evaluate()`` reads by default when `data_u8` is not it -- the pristine
+        images of an augmenting loader, whose ``data`` the training steps read (``DeviceLoader.source``)."""
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
         self.world_size, self.rank = world, rank
@@ -64,7 +67,7 @@ class FusedDDPTrainer:
             if world != 1 or comm != "xgmi":
                 raise ValueError("loopback needs world size 1 and comm='xgmi'")
             eng = NetResDeepEngine(model, data_u8, labels, EngineConfig(**args, comm="xgmi", loopback=True),
-                                   max_indices=max_indices)
+                                   max_indices=max_indices, eval_data=eval_data)
             if not eng.xgmi_selftest():
                 eng.close()
                 raise RuntimeError("xGMI loopback self-test failed")
@@ -73,7 +76,7 @@ class FusedDDPTrainer:
         if world > 1:
             broadcast_module_state(model, 0)
         if world > 1 and comm == "xgmi":
-            self.engine = self._try_xgmi(model, data_u8, labels, args, max_indices)
+            self.engine = self._try_xgmi(model, data_u8, labels, args, max_indices, eval_data)
             if self.engine is None:
                 comm = "rccl"
         if self.engine is None:
@@ -83,15 +86,17 @@ class FusedDDPTrainer:
                 dist.broadcast_object_list(obj, src=0)
                 nccl_id = obj[0]
             cfg = EngineConfig(**args, comm="rccl")
-            self.engine = NetResDeepEngine(model, data_u8, labels, cfg, nccl_id=nccl_id, max_indices=max_indices)
+            self.engine = NetResDeepEngine(model, data_u8, labels, cfg, nccl_id=nccl_id, max_indices=max_indices,
+                                           eval_data=eval_data)
         self.comm = comm if world > 1 else "none"
         self.module = model
 
-    def _try_xgmi(self, model, data_u8, labels, args, max_indices):
+    def _try_xgmi(self, model, data_u8, labels, args, max_indices, eval_data=None):
         """Create the engine with the xGMI all-reduce; None (on every rank) if any rank cannot use it."""
         eng, handle, err = None, None, None
         try:
-            eng = NetResDeepEngine(model, data_u8, labels, EngineConfig(**args, comm="xgmi"), max_indices=max_indices)
+            eng = NetResDeepEngine(model, data_u8, labels, EngineConfig(**args, comm="xgmi"), max_indices=max_indices,
+                                   eval_data=eval_data)
             handle = eng.ipc_handle()
         except Exception as ex:  # noqa: BLE001 - any failure means: fall back on every rank
             err = ex

@@ -169,7 +169,8 @@ class NetResDeepEngine:
     """Fused, graph-captured training step for NetResDeep on one MI355X (one rank of DDP)."""
 
     def __init__(self, model: nn.Module, data_u8: torch.Tensor, labels: torch.Tensor, cfg: EngineConfig,
-                 nccl_id: Optional[bytes] = None, max_indices: Optional[int] = None):
+                 nccl_id: Optional[bytes] = None, max_indices: Optional[int] = None,
+                 eval_data: Optional[torch.Tensor] = None):
         if cfg.comm not in ("rccl", "external", "xgmi"):
             raise ValueError("comm must be 'rccl', 'external' or 'xgmi'")
         if cfg.dtype not in ("bf16", "fp32"):
@@ -189,6 +190,11 @@ class NetResDeepEngine:
         self.device = dev
         assert data_u8.dtype == torch.uint8 and data_u8.dim() == 4 and tuple(data_u8.shape[1:]) == (3, 32, 32)
         self.data = data_u8.contiguous()
+        # what evaluate() reads by default: `data_u8`, unless that is an augmented view of the pristine `eval_data`
+        if eval_data is not None and (eval_data.dtype != torch.uint8 or eval_data.shape != data_u8.shape
+                                      or eval_data.device != dev):
+            raise ValueError("eval_data must be a uint8 tensor of data_u8's shape on its device")
+        self.eval_data = self.data if eval_data is None else eval_data.contiguous()
         self.labels = labels.to(device=dev, dtype=torch.int32).contiguous()
         self.flat, self.grads = bind_flat_parameters(model, dev)
         bn = model.resblocks[0].batch_norm
@@ -532,12 +538,13 @@ class NetResDeepEngine:
     # ---- evaluation -----------------------------------------------------------------------------------------
     def evaluate(self, data_u8=None, labels=None, indices=None, **kw):
         """Eval-mode accuracy / loss of the model as trained so far (``runtime/evaluate.py``), issued on the engine's
-        stream, i.e. after every step enqueued before it.  Defaults: the engine's own dataset, ``cfg.dtype``.  Reads
-        the parameters and the BatchNorm running statistics; writes nothing the engine owns."""
+        stream, i.e. after every step enqueued before it.  Defaults: the engine's own dataset (the pristine one,
+        ``eval_data``, when the engine trains on an augmented view of it), ``cfg.dtype``.  Reads the parameters and
+        the BatchNorm running statistics; writes nothing the engine owns."""
         from .evaluate import evaluate_netresdeep
         kw.setdefault("dtype", self.cfg.dtype)
         kw["stream"] = self.lib.dca_engine_stream(self.h)
-        return evaluate_netresdeep(self.model, self.data if data_u8 is None else data_u8,
+        return evaluate_netresdeep(self.model, self.eval_data if data_u8 is None else data_u8,
                                    self.labels if labels is None else labels, indices, **kw)
 
     # ---- introspection (tests) --------------------------------------------------------------------------

@@ -86,6 +86,11 @@ def _declare(lib):
     lib.dca_engine_set_lr_table.argtypes = [c_void_p, c_void_p, c_int]
     lib.dca_engine_opt_step.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]
     lib.dca_eval_netresdeep.argtypes = [c_void_p, c_void_p]  # DcaEvalArgs*, hipStream_t (runtime/evaluate.py)
+    # csrc/augment.hip (data/augment.py): src, dst, ids, n, n_rows, seed, epoch, pad, flip, hipStream_t; no engine
+    # handle, and an error string of its own
+    lib.dca_augment_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_uint, ctypes.c_uint, c_int,
+                                   c_int, c_void_p]
+    lib.dca_augment_last_error.restype = c_char_p
     lib.dca_engine_comm_time.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong),
                                          c_int]
     return lib

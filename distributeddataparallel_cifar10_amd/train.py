@@ -15,7 +15,8 @@ the same stdout lines -- while the step itself runs on the MI355X-native path:
 
 Options beyond the reference (all off by default): max_steps (per epoch), synthetic data, resume, metrics JSON,
 fault injection (``fail_at_step``), process-group timeout, set_epoch reshuffling, bf16/fp32 engine precision,
-momentum / weight decay / a per-step learning-rate schedule (``optimizer_active``; one table drives every engine).
+momentum / weight decay / a per-step learning-rate schedule (``optimizer_active``; one table drives every engine),
+``--augment`` (per-epoch random crop + flip of the training images, ``data/augment.py``).
 """
 from __future__ import annotations
 
@@ -72,6 +73,9 @@ class TrainConfig:
     lr_min: float = 0.0              # cosine: the final learning rate
     lr_step_epochs: Optional[int] = None  # step: decay every N epochs ...
     lr_gamma: float = 0.1            # ... by this factor
+    augment: bool = False            # per-epoch random crop (zero padding) + horizontal flip of the training images
+    augment_pad: int = 4             # crop padding, 0..8
+    augment_flip: bool = True
     extra: dict = field(default_factory=dict)
 
 
@@ -127,6 +131,11 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--lr-min", type=float, default=0.0, help="cosine schedule: the final learning rate")
     ap.add_argument("--lr-step-epochs", type=int, default=None, help="step schedule: decay every N epochs")
     ap.add_argument("--lr-gamma", type=float, default=0.1, help="step schedule: decay factor")
+    ap.add_argument("--augment", action="store_true",
+                    help="training images only: every epoch a fresh random crop (zero padding --augment-pad) and "
+                         "horizontal flip of each image, as one on-device pass over the uint8 dataset")
+    ap.add_argument("--augment-pad", type=int, default=4, metavar="N", help="crop padding in pixels, 0..8 (default 4)")
+    ap.add_argument("--augment-no-flip", action="store_true", help="--augment without the horizontal flip")
     return ap
 
 
@@ -149,7 +158,9 @@ def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConf
                        momentum=getattr(a, "momentum", 0.0), weight_decay=getattr(a, "weight_decay", 0.0),
                        lr_schedule=getattr(a, "lr_schedule", None), lr_warmup_steps=getattr(a, "lr_warmup_steps", 0),
                        lr_min=getattr(a, "lr_min", 0.0), lr_step_epochs=getattr(a, "lr_step_epochs", None),
-                       lr_gamma=getattr(a, "lr_gamma", 0.1))
+                       lr_gamma=getattr(a, "lr_gamma", 0.1), augment=bool(getattr(a, "augment", False)),
+                       augment_pad=getattr(a, "augment_pad", 4),
+                       augment_flip=not getattr(a, "augment_no_flip", False))
 
 
 def optimizer_active(cfg: TrainConfig) -> bool:
@@ -183,6 +194,27 @@ def engine_optimizer(cfg: TrainConfig, n_batches: int):
         return None
     from .runtime.engine import OptimizerConfig
     return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table)
+
+
+def augment_config(cfg: TrainConfig):
+    """The training loader's ``AugmentConfig`` for `cfg` (None without ``--augment``); the draws are keyed by the
+    run's seed.  Evaluation never augments."""
+    if not cfg.augment:
+        return None
+    from .data.augment import PAD_MAX, AugmentConfig
+    if not 0 <= cfg.augment_pad <= PAD_MAX:
+        raise SystemExit(f"--augment-pad must be in [0, {PAD_MAX}]")
+    return AugmentConfig(pad=cfg.augment_pad, flip=cfg.augment_flip, seed=cfg.seed)
+
+
+def make_train_loader(cfg: TrainConfig, data, labels, **kw) -> DeviceLoader:
+    """The training ``DeviceLoader`` of `cfg` (``--augment`` included); data that the augmentation cannot take fails
+    here, at start-up."""
+    aug = augment_config(cfg)
+    if aug is not None and (data.dtype != torch.uint8 or tuple(data.shape[1:]) != (3, 32, 32)):
+        raise SystemExit(f"--augment needs uint8 3x32x32 images; the dataset is {data.dtype} "
+                         f"{'x'.join(str(d) for d in data.shape[1:])}")
+    return DeviceLoader(data, labels, augment=aug, **kw)
 
 
 def optim_path(checkpoint_path: str) -> str:
@@ -317,6 +349,11 @@ def eval_only(cfg: TrainConfig, device: torch.device, rank: int = 0):
     return res
 
 
+def eval_source(loader: DeviceLoader) -> dict:
+    """``FusedDDPTrainer`` keyword for an augmenting loader: evaluate on the pristine dataset by default."""
+    return {"eval_data": loader.source} if getattr(loader, "augment", None) is not None else {}
+
+
 FUSED_BATCH_MAX = 64  # csrc/common.h BMAX_LIMIT: per-rank batch the fused NetResDeep engine supports
 
 
@@ -406,6 +443,10 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
         if fused:
             bs = train_loader.batch_size
             idx = train_loader.indices()[:steps_per_epoch * bs]
+            if getattr(train_loader, "augment", None) is not None:
+                # this epoch's crops and flips of the rows the epoch reads, on the engine's stream: after the last
+                # epoch's steps and before set_indices, which stages the first batch from `data`
+                train_loader.augment_epoch(idx, stream=model.engine.lib.dca_engine_stream(model.engine.h))
             if cfg.fail_at_step is not None and global_step < cfg.fail_at_step <= global_step + steps_per_epoch:
                 done = cfg.fail_at_step - global_step - 1  # steps before the failing one still run, as on the
                 if done:                                   # generic path (the failure is raised AT that step)
@@ -455,6 +496,7 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                    allreduce_us_per_step=(comm_us / comm_n) if comm_n else None,
                    engine=getattr(eng, "kind_name", cfg.engine if not fused else None),
                    lr=last_lr,  # the learning rate of the epoch's last step
+                   augment=_augment_record(train_loader),
                    dtype=cfg.dtype, fp32_mode=("3xbf16" if getattr(eng, "kind_name", "") == "sliced" else
                                                "fp32-mfma") if cfg.dtype == "fp32" and fused else None,
                    **ev_rec)
@@ -480,6 +522,11 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
     nbt = _num_batches_tracked(unwrap(model))
     mlog.write(final=True, steps_total=global_step, seconds_total=total, num_batches_tracked=nbt)
     return {"losses": history, "seconds": total, "steps": global_step, "num_batches_tracked": nbt}
+
+
+def _augment_record(loader) -> Optional[dict]:
+    a = getattr(loader, "augment", None)
+    return None if a is None else {"pad": a.pad, "flip": bool(a.flip), "seed": a.seed}
 
 
 def _num_batches_tracked(module) -> Optional[int]:
@@ -559,8 +606,10 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
         return FlatBucketDDP(OpsModel(model, fp8=cfg.fp8), bucket_cap_mb=cfg.bucket_mb)
     if kind == "fused":
         n_idx = len(loader) * loader.batch_size
+        # loader.data: with --augment the per-epoch augmented view (fixed address); loader.source, the pristine
+        # dataset, is then what engine.evaluate() reads by default
         return FusedDDPTrainer(model, loader.data, loader.labels, batch_max=loader.batch_size, lr=cfg.lr,
                                dtype=cfg.dtype, max_indices=max(n_idx, loader.batch_size), comm=cfg.allreduce,
-                               optimizer=engine_optimizer(cfg, len(loader)))
+                               optimizer=engine_optimizer(cfg, len(loader)), **eval_source(loader))
     return FlatBucketDDP(model, bucket_cap_mb=cfg.bucket_mb)
 

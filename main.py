@@ -20,10 +20,10 @@ import sys
 import torch
 import torch.multiprocessing as mp
 
-from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader
+from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader  # noqa: F401
 from distributeddataparallel_cifar10_amd.parallel import dist as pdist
 from distributeddataparallel_cifar10_amd.train import (TrainConfig, add_cli_args, build_model_for_rank,
-                                                       config_from_args, eval_only, load_dataset)
+                                                       config_from_args, eval_only, load_dataset, make_train_loader)
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 from distributeddataparallel_cifar10_amd.utils.gpu import free_gpu_cache  # noqa: F401  (reference main.py:67)
 
@@ -50,8 +50,8 @@ def main(rank, world_size, cfg=None):
             eval_only(cfg, device, rank)
             return
         data, labels = load_dataset(cfg)
-        loader = DeviceLoader(data, labels, batch_size=cfg.batch_size, world_size=world_size, rank=rank,
-                              device=device, sampler="distributed", seed=0, set_epoch=cfg.set_epoch)
+        loader = make_train_loader(cfg, data, labels, batch_size=cfg.batch_size, world_size=world_size, rank=rank,
+                                   device=device, sampler="distributed", seed=0, set_epoch=cfg.set_epoch)
         model = build_model_for_rank(cfg, rank, world_size, device, data, labels, loader)
         train_loop(model, train_loader=loader, rank=rank, cfg=cfg)
         if hasattr(model, "close"):

@@ -17,10 +17,11 @@ import argparse
 
 import torch
 
-from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader
+from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader  # noqa: F401
 from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
 from distributeddataparallel_cifar10_amd.train import TrainConfig, add_cli_args, config_from_args, load_dataset
-from distributeddataparallel_cifar10_amd.train import engine_optimizer, eval_only, resolve_engine
+from distributeddataparallel_cifar10_amd.train import engine_optimizer, eval_only, eval_source, make_train_loader
+from distributeddataparallel_cifar10_amd.train import resolve_engine
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 
 data_path = '../data/CIFAR-10/'  # reference main_no_ddp.py:17
@@ -33,8 +34,8 @@ _cfg = TrainConfig(data_path=data_path, batch_size=64, checkpoint=False)
 def prepare(batch_size=32, pin_memory=False, num_workers=0):
     """Reference main_no_ddp.py:22-34: the arguments are ignored; batch 64, reshuffled every epoch."""
     data, labels = load_dataset(_cfg)
-    train_loader = DeviceLoader(data, labels, batch_size=_cfg.batch_size, device=device, sampler="random",
-                                seed=_cfg.seed if _cfg.synthetic else None)
+    train_loader = make_train_loader(_cfg, data, labels, batch_size=_cfg.batch_size, device=device, sampler="random",
+                                     seed=_cfg.seed if _cfg.synthetic else None)
     print(len(train_loader))
     return train_loader
 
@@ -51,7 +52,8 @@ def training_loop(model, train_loader):
         # device with fewer CUs, still falls back to the multi-kernel engine with a warning.
         model = FusedDDPTrainer(model, train_loader.data, train_loader.labels, batch_max=train_loader.batch_size,
                                 lr=_cfg.lr, dtype=_cfg.dtype, max_indices=max(n_idx, train_loader.batch_size),
-                                full_device=True, optimizer=engine_optimizer(_cfg, len(train_loader)))
+                                full_device=True, optimizer=engine_optimizer(_cfg, len(train_loader)),
+                                **eval_source(train_loader))
     elif kind == "ops":  # the ops-layer HIP kernels (flat parameters, packed weights, HIP SGD)
         from distributeddataparallel_cifar10_amd.ops.models import OpsModel
         from distributeddataparallel_cifar10_amd.parallel.flat_ddp import FlatBucketDDP

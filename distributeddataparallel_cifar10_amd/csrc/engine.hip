@@ -143,6 +143,7 @@ struct Engine {
   OptDev* optdev = nullptr;     // device copy: hyper-parameters, step counter, ticket
   OptDev opt{};                 // host mirror of the hyper-parameters (step / ticket live on the device only)
   float* lr_table = nullptr;    // device learning-rate table (owned)
+  bool ema_on = false;          // the pass runs in its EMA form (dca_engine_set_ema; opt.ema is then set)
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -289,7 +290,7 @@ static int enqueue_xgmi(Engine* e, const Ctx& cx, float* dst, int apply) {
 // The optimiser pass over the flat buffer (momentum, weight decay, the step's learning rate; derived weight copies;
 // CC4 base) -- in place of the step's own SGD when an optimiser is set.
 static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
-  HIPCK(launch_apply_opt(e->bf, cx, e->optdev, e->st));
+  HIPCK(launch_apply_opt(e->bf, e->ema_on, cx, e->optdev, e->st));
   return 0;
 }
 
@@ -1048,7 +1049,11 @@ int dca_engine_set_optimizer(void* h, float* momentum_buf, float mu, float wd) {
   const bool on = momentum_buf != nullptr;
   if (on != e->opt_on) drop_graphs(e);
   e->opt_on = false;  // (on again below, once the device block is complete)
-  if (!on) return 0;
+  if (!on) {  // the EMA form goes with the pass
+    e->ema_on = false;
+    e->opt.ema = nullptr;
+    return 0;
+  }
   if (e->optdev == nullptr) {  // first use: step 0, ticket 0, no table
     e->opt = dca::OptDev{};
     e->opt.lr_const = e->in.lr;
@@ -1101,6 +1106,38 @@ int dca_engine_set_lr_table(void* h, const float* values, int n) {
   e->opt.n_table = n;
   HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
   if (old) (void)hipFree(old);
+  return 0;
+}
+
+// EMA form of the optimiser pass: after every update the pass also averages the model into `ema_buf`, a flat fp32
+// [FLAT_ALLOC] device buffer owned by the caller in the gradient buffer's layout (the caller fills it with the model
+// to start from): e = p' + d * (e - p') over the parameters and over running_mean | running_var, d = `decay` or, with
+// `warmup`, min(decay, (1 + k) / (10 + k)) at optimiser step k.  Needs the optimiser on; null turns the form off.
+// Switching it on or off drops the captured graphs (another kernel); a new decay, warm-up flag or buffer on a running
+// EMA reaches them as it is (device memory).  Synchronous.
+int dca_engine_set_ema(void* h, float* ema_buf, float decay, int warmup) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on) {
+    g_err = "set_ema: no optimiser set (dca_engine_set_optimizer first)";
+    return -1;
+  }
+  if (ema_buf && !(decay >= 0.f && decay < 1.f)) {
+    g_err = "set_ema: the decay must lie in [0, 1)";
+    return -1;
+  }
+  if (ema_buf && ((uintptr_t)ema_buf % 16)) {
+    g_err = "set_ema: the EMA buffer must be 16-byte aligned";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  const bool on = ema_buf != nullptr;
+  if (on != e->ema_on) drop_graphs(e);
+  e->ema_on = false;  // (on again below, once the device block holds the buffer)
+  e->opt.ema = ema_buf;
+  e->opt.ema_decay = on ? decay : 0.f;
+  e->opt.ema_warmup = on && warmup ? 1 : 0;
+  HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
+  e->ema_on = on;
   return 0;
 }
 

@@ -15,6 +15,13 @@
 // lr_table[min(step, n_table - 1)] (lr_const without a table); `step` is the pass's own device counter (the
 // engine's step_count is cleared at every epoch's loss read) and advances once per launch, by the workgroup that
 // takes the last ticket -- every workgroup reads `step` before it takes its ticket.
+//
+// The EMA form (k_apply_opt<BF, true>; dca_engine_set_ema) also keeps an exponential moving average of the model in a
+// second flat buffer of the gradient buffer's layout: with the fresh p in registers, e = fmaf(d, e - p, p) over
+// [0, OFF_RS), and the same update of cx.rm | cx.rv (the module's running statistics as the step left them) into
+// [OFF_RS, OFF_RS + 64) by the 64 threads that write the CC4 base.  d = ema_decay, or with warm-up
+// min(ema_decay, (1 + step) / (10 + step)), computed by thread 0 from the `step` it reads anyway.  The form without
+// EMA compiles to what the pass was before the EMA form existed.
 // A translation unit of its own (see optimizer.h); derive_param comes from netresdeep_kernels.hip.
 #include "netresdeep_kernels.hip"
 #include "optimizer.h"
@@ -25,19 +32,30 @@ constexpr int OPT_V4 = OFF_RS / 4;                  // 19019 float4 (every tenso
 constexpr int OPT_NB = (OPT_V4 + NT - 1) / NT;      // 75 workgroups, one float4 per thread
 static_assert(OFF_RS % 4 == 0, "the parameter range must be float4 granular");
 
-template <bool BF>
+template <bool BF, bool EMA>
 __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
   __shared__ float s_lr;
   __shared__ int s_step;
+  __shared__ float s_ema;  // (EMA form only: unused, and so not allocated, in the other)
   const int t = threadIdx.x, v = blockIdx.x * NT + t;
   if (t == 0) {
     const int st = __hip_atomic_load(&od->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int n = od->n_table;
     s_step = st;
     s_lr = n > 0 ? od->lr_table[st < n - 1 ? (st < 0 ? 0 : st) : n - 1] : od->lr_const;
+    if constexpr (EMA) {
+      float d = od->ema_decay;
+      if (od->ema_warmup) {
+        const float k = (float)(st < 0 ? 0 : st);
+        d = fminf(d, (1.f + k) / (10.f + k));
+      }
+      s_ema = d;
+    }
   }
   const float mu = od->mu, wd = od->wd;
   float* mbuf = od->buf;
+  float* ebuf = nullptr;
+  if constexpr (EMA) ebuf = od->ema;
   __syncthreads();
   const float lr = s_lr;
   if (v < OPT_V4) {
@@ -45,6 +63,8 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
     const f32x4 g = *(const f32x4*)(cx.grads + e0);
     f32x4 p = *(const f32x4*)(cx.params + e0);
     f32x4 m = *(const f32x4*)(mbuf + e0);
+    f32x4 a;
+    if constexpr (EMA) a = *(const f32x4*)(ebuf + e0);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float d = __builtin_fmaf(wd, p[k], g[k] * cx.inv_ws);
@@ -53,11 +73,24 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
     }
     *(f32x4*)(mbuf + e0) = m;
     *(f32x4*)(cx.params + e0) = p;
+    if constexpr (EMA) {
+      const float dk = s_ema;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = __builtin_fmaf(dk, a[k] - p[k], p[k]);
+      *(f32x4*)(ebuf + e0) = a;
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) derive_param<BF>(cx, e0 + k, p[k]);
   }
   // CC4: rank 0's running statistics (the tail of the all-reduced buffer) become every rank's base
   if (cx.ws > 1 && v < 64) cx.rs_base[v] = cx.grads[OFF_RS + v];
+  if constexpr (EMA) {  // the averaged running statistics: rm | rv into the layout's CC4 tail, nothing beyond it
+    if (v < 64) {
+      float* er = ebuf + OFF_RS + v;
+      const float s = v < 32 ? cx.rm[v] : cx.rv[v - 32];
+      *er = __builtin_fmaf(s_ema, *er - s, s);
+    }
+  }
   if (t == 0) {  // the last workgroup to arrive advances the step (all have read it: their tickets are taken after)
     const unsigned prev = __hip_atomic_fetch_add(&od->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (prev == gridDim.x - 1) {
@@ -68,9 +101,10 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
   }
 }
 
-hipError_t launch_apply_opt(bool bf, const Ctx& cx, OptDev* od, hipStream_t st) {
-  if (bf) hipLaunchKernelGGL(k_apply_opt<true>, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
-  else hipLaunchKernelGGL(k_apply_opt<false>, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
+hipError_t launch_apply_opt(bool bf, bool ema, const Ctx& cx, OptDev* od, hipStream_t st) {
+  auto* k = bf ? k_apply_opt<true, false> : k_apply_opt<false, false>;
+  if (ema) k = bf ? k_apply_opt<true, true> : k_apply_opt<false, true>;
+  hipLaunchKernelGGL(k, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
   return hipGetLastError();
 }
 

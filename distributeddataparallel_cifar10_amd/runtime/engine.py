@@ -131,10 +131,14 @@ class OptimizerConfig:
     """SGD with momentum and weight decay on a per-step learning rate, run by the engine's optimiser pass
     (``csrc/optimizer.hip``) after each step's gradient reduction -- torch ``SGD(momentum, weight_decay)`` with
     dampening 0 and decay on every tensor.  ``lr_table``: one learning rate per optimiser step (the last entry holds
-    beyond its end; ``utils/schedule.py`` builds them); ``None``: the engine's constant ``lr``."""
+    beyond its end; ``utils/schedule.py`` builds them); ``None``: the engine's constant ``lr``.  ``ema_decay``: the pass
+    also keeps an exponential moving average of the parameters and the BatchNorm running statistics
+    (``utils/ema.py``; ``ema_warmup``: decay ``min(ema_decay, (1 + k) / (10 + k))`` at step k); ``None``: no average."""
     momentum: float = 0.0
     weight_decay: float = 0.0
     lr_table: Optional[Sequence[float]] = None
+    ema_decay: Optional[float] = None
+    ema_warmup: bool = False
 
 
 @dataclass
@@ -242,6 +246,7 @@ class NetResDeepEngine:
         self.derive()
         self._n_indices = 0
         self.momentum = None  # flat fp32 momentum buffer (optimiser mode), laid out like `flat` and `grads`
+        self.ema = None  # flat fp32 [FLAT_ALLOC] average (EMA on), laid out like `grads`: running stats at OFF_RS
         if cfg.optimizer is not None:
             self.set_optimizer(cfg.optimizer)
 
@@ -252,6 +257,7 @@ class NetResDeepEngine:
         if opt is None:
             native.check(self.lib.dca_engine_set_optimizer(self.h, None, 0.0, 0.0), "dca_engine_set_optimizer")
             self.cfg.optimizer = None
+            self.ema = None  # (the EMA form goes with the pass)
             return
         if opt.momentum < 0 or opt.weight_decay < 0:
             raise ValueError("momentum and weight_decay must not be negative")
@@ -263,6 +269,8 @@ class NetResDeepEngine:
         self.cfg.optimizer = opt
         if opt.lr_table is not None:
             self.set_lr_table(opt.lr_table)
+        if opt.ema_decay is not None or self.ema is not None:
+            self.set_ema_decay(opt.ema_decay, opt.ema_warmup)
 
     def set_lr_table(self, values) -> None:
         """Per-step learning rates: optimiser step k uses ``values[min(k, len - 1)]``; an empty table returns to the
@@ -304,6 +312,90 @@ class NetResDeepEngine:
         torch.cuda.synchronize(self.device)
         v = ctypes.c_int(int(state["step"]))
         native.check(self.lib.dca_engine_opt_step(self.h, 1, ctypes.byref(v)), "dca_engine_opt_step")
+
+    # ---- EMA of the weights (the optimiser pass's EMA form) --------------------------------------------------
+    def set_ema_decay(self, decay: Optional[float], warmup: Optional[bool] = None) -> None:
+        """A new decay (and warm-up flag; ``None`` keeps it) for the average.  On a running EMA the captured step
+        graphs pick it up without re-capture; on an engine without one this switches EMA on -- the buffer is allocated
+        and starts as a copy of the model (``reset_ema``) -- and ``decay=None`` switches it off and frees the buffer
+        (either switch drops the captured graphs)."""
+        from ..utils.ema import check_decay
+        self._need_optimizer()
+        opt = self.cfg.optimizer
+        if decay is None:
+            native.check(self.lib.dca_engine_set_ema(self.h, None, 0.0, 0), "dca_engine_set_ema")
+            self.ema, opt.ema_decay = None, None
+            return
+        decay = check_decay(decay)
+        warmup = bool(opt.ema_warmup if warmup is None else warmup)
+        fresh = self.ema is None
+        if fresh:
+            self.ema = torch.zeros(FLAT_ALLOC, dtype=torch.float32, device=self.device)
+            self.reset_ema()
+        try:
+            native.check(self.lib.dca_engine_set_ema(self.h, self.ema.data_ptr(), decay, 1 if warmup else 0),
+                         "dca_engine_set_ema")
+        except RuntimeError:
+            if fresh:
+                self.ema = None
+            raise
+        opt.ema_decay, opt.ema_warmup = decay, warmup
+
+    def _need_ema(self) -> None:
+        if self.ema is None:
+            raise RuntimeError("no EMA: OptimizerConfig(ema_decay=...) or set_ema_decay()")
+
+    def reset_ema(self) -> None:
+        """Restart the average from the model as it is now: the parameters and the running statistics are copied in."""
+        self._need_ema()
+        self.sync()
+        with torch.no_grad():
+            self.ema[:OFF_RS].copy_(self.flat[:OFF_RS])
+            self.ema[OFF_RS:OFF_RS + 32].copy_(self.bn.running_mean)
+            self.ema[OFF_RS + 32:OFF_RS + 64].copy_(self.bn.running_var)
+        torch.cuda.synchronize(self.device)
+
+    def _ema_views(self) -> dict:
+        """{unique tensor name: view of the averaged buffer} -- the nine parameters through ``LAYOUT`` and the two
+        running statistics at ``OFF_RS``."""
+        out = {name: self.ema[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
+        out["resblocks.0.batch_norm.running_mean"] = self.ema[OFF_RS:OFF_RS + 32]
+        out["resblocks.0.batch_norm.running_var"] = self.ema[OFF_RS + 32:OFF_RS + 64]
+        return out
+
+    def ema_state_dict(self) -> dict:
+        """The averaged model under the keys of the module's ``state_dict`` (66 for NetResDeep: it loads strictly into
+        the reference model): the float tensors are views of the averaged buffer (clone them to keep a snapshot),
+        ``num_batches_tracked`` is a copy of the live counter.  Synchronises."""
+        self._need_ema()
+        self.sync()
+        views = self._ema_views()
+        live = self.model.state_dict()
+        nbt = self.bn.num_batches_tracked.detach().clone()
+        out = type(live)()
+        for key in live:
+            name = _unique_name(key)
+            out[key] = nbt if name.endswith("num_batches_tracked") else views[name]
+        if hasattr(live, "_metadata"):
+            out._metadata = live._metadata
+        return out
+
+    def load_ema_state_dict(self, state: dict) -> None:
+        """Restore ``ema_state_dict()`` output (tensors on any device; ``num_batches_tracked`` is not part of the
+        average and is ignored)."""
+        self._need_ema()
+        views = self._ema_views()
+        missing = [k for k in views if k not in state]
+        if missing:
+            raise ValueError(f"EMA state lacks {missing}")
+        self.sync()
+        with torch.no_grad():
+            for name, view in views.items():
+                t = state[name]
+                if tuple(t.shape) != tuple(view.shape):
+                    raise ValueError(f"{name}: expected shape {tuple(view.shape)}, got {tuple(t.shape)}")
+                view.copy_(t.detach().to(self.device, torch.float32))
+        torch.cuda.synchronize(self.device)
 
     # ---- carried step state ---------------------------------------------------------------------------------
     def step_state(self) -> dict:
@@ -536,12 +628,19 @@ class NetResDeepEngine:
         return self.read_loss(reset=True)
 
     # ---- evaluation -----------------------------------------------------------------------------------------
-    def evaluate(self, data_u8=None, labels=None, indices=None, **kw):
+    def evaluate(self, data_u8=None, labels=None, indices=None, ema: bool = False, **kw):
         """Eval-mode accuracy / loss of the model as trained so far (``runtime/evaluate.py``), issued on the engine's
         stream, i.e. after every step enqueued before it.  Defaults: the engine's own dataset (the pristine one,
         ``eval_data``, when the engine trains on an augmented view of it), ``cfg.dtype``.  Reads the parameters and
-        the BatchNorm running statistics; writes nothing the engine owns."""
+        the BatchNorm running statistics; writes nothing the engine owns.  `ema`: the averaged parameters and (unless
+        ``bn_stats=`` is given) the averaged running statistics instead, read where they lie in the EMA buffer."""
         from .evaluate import evaluate_netresdeep
+        if ema:
+            self._need_ema()
+            views = self._ema_views()
+            kw["params"] = {name: views[name] for name in LAYOUT}
+            kw.setdefault("bn_stats", (views["resblocks.0.batch_norm.running_mean"],
+                                       views["resblocks.0.batch_norm.running_var"]))
         kw.setdefault("dtype", self.cfg.dtype)
         kw["stream"] = self.lib.dca_engine_stream(self.h)
         return evaluate_netresdeep(self.model, self.eval_data if data_u8 is None else data_u8,
@@ -583,6 +682,15 @@ class NetResDeepEngine:
             self.close()
         except Exception:
             pass
+
+
+def _unique_name(key: str) -> str:
+    """state_dict key -> the name of the one tensor behind it (NetResDeep applies ONE ResBlock ten times, so
+    ``resblocks.7.conv.weight`` is ``resblocks.0.conv.weight``)."""
+    parts = key.split(".")
+    if parts[0] == "resblocks":
+        parts[1] = "0"
+    return ".".join(parts)
 
 
 def _copy_from_ptr(out: torch.Tensor, ptr: int) -> None:

@@ -83,14 +83,15 @@ def _stream_of(stream, device):
 
 def evaluate_netresdeep(model, data_u8: torch.Tensor, labels: torch.Tensor, indices=None, dtype: str = "fp32",
                         return_logits: bool = False, max_workgroups: int = 0, stream=None,
-                        bn_stats=None) -> EvalResult:
+                        bn_stats=None, params=None) -> EvalResult:
     """Evaluate NetResDeep `model` in eval mode (BatchNorm running statistics) on ``data_u8[indices]``.
 
     `dtype` selects the kernel's precision on a GPU model ("bf16": bf16 conv operands and fc1 weight; "fp32":
     3xbf16 conv, fp32 elsewhere); the CPU path is plain fp32.  `max_workgroups` caps the grid (0: the whole device);
     the result does not depend on it.  `bn_stats` = (running_mean, running_var) replaces the module's own running
-    statistics for this call (``evaluate_distributed``: rank 0's).  Nothing of the model is modified: parameters,
-    buffers and training flags are as before."""
+    statistics for this call (``evaluate_distributed``: rank 0's); `params` = {parameter name: tensor}, all nine of
+    ``named_parameters()``, replaces the module's parameters in the same way (an averaged copy, ``utils/ema.py``).
+    Nothing of the model is modified: parameters, buffers and training flags are as before."""
     if dtype not in ("bf16", "fp32"):
         raise ValueError("dtype must be 'bf16' or 'fp32'")
     net = unwrap(model)
@@ -105,15 +106,24 @@ def evaluate_netresdeep(model, data_u8: torch.Tensor, labels: torch.Tensor, indi
     if idx.size == 0:
         raise ValueError("nothing to evaluate")
     dev = net.fc1.weight.device
+    if params is not None:
+        named = dict(net.named_parameters())
+        if set(params) != set(named):
+            raise ValueError(f"params must cover exactly {sorted(named)}")
+        for name, p in named.items():
+            if tuple(params[name].shape) != tuple(p.shape):
+                raise ValueError(f"params[{name!r}] has shape {tuple(params[name].shape)}, expected {tuple(p.shape)}")
     if dev.type != "cuda":
-        return _evaluate_cpu(net, data_u8, labels, idx, return_logits, bn_stats)
-    return _evaluate_gpu(net, data_u8, labels, idx, dtype, return_logits, int(max_workgroups), stream, dev, bn_stats)
+        return _evaluate_cpu(net, data_u8, labels, idx, return_logits, bn_stats, params)
+    return _evaluate_gpu(net, data_u8, labels, idx, dtype, return_logits, int(max_workgroups), stream, dev, bn_stats,
+                         params)
 
 
-def _evaluate_cpu(net, data_u8, labels, idx, return_logits, bn_stats) -> EvalResult:
+def _evaluate_cpu(net, data_u8, labels, idx, return_logits, bn_stats, params=None) -> EvalResult:
     flags = [(m, m.training) for m in net.modules()]
     bn = net.resblocks[0].batch_norm
     own = (bn.running_mean, bn.running_var)
+    own_p = [(p, p.data) for _, p in net.named_parameters()] if params is not None else []
     data_u8, labels = data_u8.cpu(), labels.cpu().long()
     sel = torch.from_numpy(idx.astype(np.int64))
     outs = []
@@ -121,11 +131,16 @@ def _evaluate_cpu(net, data_u8, labels, idx, return_logits, bn_stats) -> EvalRes
         net.eval()
         if bn_stats is not None:
             bn.running_mean, bn.running_var = (t.to(own[0].device, torch.float32) for t in bn_stats)
+        if params is not None:
+            for name, p in net.named_parameters():
+                p.data = params[name].detach().to(p.device, p.dtype)
         with torch.no_grad():
             for s in range(0, len(sel), CPU_CHUNK):
                 outs.append(net(normalize_u8(data_u8.index_select(0, sel[s:s + CPU_CHUNK]))).float())
     finally:
         bn.running_mean, bn.running_var = own
+        for p, was in own_p:
+            p.data = was
         for m, was in flags:
             m.training = was
     logits = torch.cat(outs)
@@ -136,7 +151,8 @@ def _evaluate_cpu(net, data_u8, labels, idx, return_logits, bn_stats) -> EvalRes
                    logits if return_logits else None, loss)
 
 
-def _evaluate_gpu(net, data_u8, labels, idx, dtype, return_logits, max_workgroups, stream, dev, bn_stats) -> EvalResult:
+def _evaluate_gpu(net, data_u8, labels, idx, dtype, return_logits, max_workgroups, stream, dev, bn_stats,
+                  params=None) -> EvalResult:
     from . import native
     lib = native.require_native()
     bn = net.resblocks[0].batch_norm
@@ -144,8 +160,11 @@ def _evaluate_gpu(net, data_u8, labels, idx, dtype, return_logits, max_workgroup
     # inputs made on torch's current stream (uploads, casts) are ordered before the kernel on `st`; the outputs are
     # allocated, written and reduced on `st`, and the one host copy at the end waits for all of it
     with torch.cuda.device(dev):
-        tensors = [net.conv1.weight, net.conv1.bias, net.resblocks[0].conv.weight, bn.weight, bn.bias,
-                   *(bn_stats or (bn.running_mean, bn.running_var)), net.fc1.weight, net.fc1.bias, net.fc2.weight, net.fc2.bias]
+        par = params if params is not None else dict(net.named_parameters())
+        tensors = [par["conv1.weight"], par["conv1.bias"], par["resblocks.0.conv.weight"],
+                   par["resblocks.0.batch_norm.weight"], par["resblocks.0.batch_norm.bias"],
+                   *(bn_stats or (bn.running_mean, bn.running_var)), par["fc1.weight"], par["fc1.bias"],
+                   par["fc2.weight"], par["fc2.bias"]]
         shapes = [(32, 3, 3, 3), (32,), (32, 32, 3, 3), (32,), (32,), (32,), (32,), (32, 2048), (32,), (10, 32), (10,)]
         held = []
         for t, shape in zip(tensors, shapes):
@@ -210,7 +229,7 @@ def eval_shard(n: int, world_size: int, rank: int) -> np.ndarray:
 
 
 def evaluate_distributed(model, data_u8: torch.Tensor, labels: torch.Tensor, indices=None, evaluate=None,
-                         sync_bn_stats: bool = True, **kw) -> EvalResult:
+                         sync_bn_stats: bool = True, bn_stats_src=None, **kw) -> EvalResult:
     """Evaluate this rank's shard and all-reduce (correct, count, loss_sum) over ``torch.distributed`` (SUM; one
     process without a process group evaluates everything).  Collective: every rank calls it with the same
     `indices`.  `evaluate` replaces ``evaluate_netresdeep`` (e.g. an engine's bound ``evaluate``, which takes the
@@ -218,7 +237,9 @@ def evaluate_distributed(model, data_u8: torch.Tensor, labels: torch.Tensor, ind
 
     Between two steps the ranks' BatchNorm running statistics differ (DDP broadcasts rank 0's at the next forward,
     and rank 0's are what a checkpoint holds), so with `sync_bn_stats` every rank evaluates with a copy of rank 0's
-    (``bn_stats=``; the modules' own buffers are not touched): the result is that of rank 0's model on all images."""
+    (``bn_stats=``; the modules' own buffers are not touched): the result is that of rank 0's model on all images.
+    `bn_stats_src`: this rank's (running_mean, running_var) to take in place of the module's -- averaged statistics
+    (``utils/ema.py``), which differ between the ranks just as the live ones do."""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     ws, rank = (dist.get_world_size(), dist.get_rank()) if on else (1, 0)
@@ -226,7 +247,8 @@ def evaluate_distributed(model, data_u8: torch.Tensor, labels: torch.Tensor, ind
     cpu_group = on and dist.get_backend() == "gloo"
     if on and ws > 1 and sync_bn_stats:
         bn = net.resblocks[0].batch_norm
-        stats = torch.cat([bn.running_mean.detach().float(), bn.running_var.detach().float()])
+        src = bn_stats_src if bn_stats_src is not None else (bn.running_mean, bn.running_var)
+        stats = torch.cat([src[0].detach().float().reshape(-1), src[1].detach().float().reshape(-1)])
         stats = stats.cpu() if cpu_group else stats.clone()
         dist.broadcast(stats, 0)
         stats = stats.to(bn.running_mean.device)

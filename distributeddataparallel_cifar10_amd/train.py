@@ -16,12 +16,15 @@ the same stdout lines -- while the step itself runs on the MI355X-native path:
 Options beyond the reference (all off by default): max_steps (per epoch), synthetic data, resume, metrics JSON,
 fault injection (``fail_at_step``), process-group timeout, set_epoch reshuffling, bf16/fp32 engine precision,
 momentum / weight decay / a per-step learning-rate schedule (``optimizer_active``; one table drives every engine),
-``--augment`` (per-epoch random crop + flip of the training images, ``data/augment.py``).
+``--augment`` (per-epoch random crop + flip of the training images, ``data/augment.py``), ``--ema-decay`` (an
+exponential moving average of the weights, ``utils/ema.py``: kept by the fused engine's optimiser pass on the device, by
+``ModelEma`` on the other engines; evaluated beside the live model and saved as ``<checkpoint>.ema.pt``).
 """
 from __future__ import annotations
 
 import argparse
 import os
+import sys
 import time
 from dataclasses import dataclass, field
 from typing import Optional
@@ -76,6 +79,8 @@ class TrainConfig:
     augment: bool = False            # per-epoch random crop (zero padding) + horizontal flip of the training images
     augment_pad: int = 4             # crop padding, 0..8
     augment_flip: bool = True
+    ema_decay: Optional[float] = None  # None: no average; D in [0, 1): EMA of the weights (see optimizer_active())
+    ema_warmup: bool = False         # decay min(D, (1 + k) / (10 + k)) at optimiser step k
     extra: dict = field(default_factory=dict)
 
 
@@ -136,6 +141,12 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
                          "horizontal flip of each image, as one on-device pass over the uint8 dataset")
     ap.add_argument("--augment-pad", type=int, default=4, metavar="N", help="crop padding in pixels, 0..8 (default 4)")
     ap.add_argument("--augment-no-flip", action="store_true", help="--augment without the horizontal flip")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the parameters and BatchNorm running statistics with "
+                         "decay D in [0, 1), updated after every optimiser step; --eval also reports it and every "
+                         "checkpoint gets a <checkpoint>.ema.pt beside it (default: off)")
+    ap.add_argument("--ema-warmup", action="store_true",
+                    help="--ema-decay with the decay min(D, (1 + k) / (10 + k)) at optimiser step k")
     return ap
 
 
@@ -160,13 +171,24 @@ def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConf
                        lr_min=getattr(a, "lr_min", 0.0), lr_step_epochs=getattr(a, "lr_step_epochs", None),
                        lr_gamma=getattr(a, "lr_gamma", 0.1), augment=bool(getattr(a, "augment", False)),
                        augment_pad=getattr(a, "augment_pad", 4),
-                       augment_flip=not getattr(a, "augment_no_flip", False))
+                       augment_flip=not getattr(a, "augment_no_flip", False),
+                       ema_decay=_ema_decay_arg(getattr(a, "ema_decay", None)),
+                       ema_warmup=bool(getattr(a, "ema_warmup", False)))
+
+
+def _ema_decay_arg(decay):
+    if decay is not None and not 0.0 <= decay < 1.0:
+        raise SystemExit("--ema-decay must lie in [0, 1)")
+    return decay
 
 
 def optimizer_active(cfg: TrainConfig) -> bool:
     """Whether any optimiser option beyond the reference's SGD(lr) is on.  Off (the default): the fused engine runs
-    its own fused SGD (``optimizer=None``) and the other engines build FlatSGD(model, lr) / torch.optim.SGD(lr)."""
-    return bool(cfg.momentum or cfg.weight_decay or cfg.lr_schedule is not None or cfg.lr_warmup_steps)
+    its own fused SGD (``optimizer=None``) and the other engines build FlatSGD(model, lr) / torch.optim.SGD(lr).
+    ``--ema-decay`` alone turns it on too: the fused engine keeps the average in its optimiser pass, so it then takes
+    the split step form (with a constant table if no schedule is given)."""
+    return bool(cfg.momentum or cfg.weight_decay or cfg.lr_schedule is not None or cfg.lr_warmup_steps
+                or cfg.ema_decay is not None)
 
 
 def steps_per_epoch_of(cfg: TrainConfig, n_batches: int) -> int:
@@ -193,7 +215,8 @@ def engine_optimizer(cfg: TrainConfig, n_batches: int):
     if table is None:
         return None
     from .runtime.engine import OptimizerConfig
-    return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table)
+    return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table,
+                           ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
 
 
 def augment_config(cfg: TrainConfig):
@@ -308,16 +331,31 @@ def eval_line(epoch: int, accuracy: float, mean_loss: float) -> str:
     return "Epoch {}, Test accuracy {:.4f}, Test loss {}".format(epoch, accuracy, mean_loss)
 
 
-def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False):
+def eval_line_ema(epoch: int, accuracy: float, mean_loss: float) -> str:
+    return "Epoch {}, EMA test accuracy {:.4f}, EMA test loss {}".format(epoch, accuracy, mean_loss)
+
+
+def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False, ema=None):
     """Eval-mode result of `model` on (data, labels), sharded over the ranks of the process group (collective).
     A ``FusedDDPTrainer`` evaluates with the fused kernel on its engine's stream; `kernel`: a bare NetResDeep on a GPU,
     the same kernel with no engine; every other model (``FlatBucketDDP``, ``OpsModel``, stock ops) runs as the module in
-    eval mode."""
+    eval mode.  `ema`: evaluate the averaged model instead -- ``True`` for a ``FusedDDPTrainer`` (its engine's
+    average, read in place), the ``ModelEma`` of any other model (swapped into the module for the call); every rank
+    evaluates with rank 0's averaged running statistics, as with the live ones."""
     from .parallel.ddp import FusedDDPTrainer
     from .parallel.flat_ddp import FlatBucketDDP
     from .runtime.evaluate import evaluate_distributed, evaluate_module
     if isinstance(model, FusedDDPTrainer):
+        if ema:
+            from .runtime.engine import OFF_RS
+            avg = model.engine.ema
+            return evaluate_distributed(model.module, data, labels, bn_stats_src=(avg[OFF_RS:OFF_RS + 32],
+                                                                                   avg[OFF_RS + 32:OFF_RS + 64]),
+                                        evaluate=lambda d, l, i, **kw: model.engine.evaluate(d, l, i, ema=True, **kw))
         return evaluate_distributed(model.module, data, labels, evaluate=model.engine.evaluate)
+    if ema is not None:
+        with ema.swapped_in():
+            return run_eval(model, data, labels, cfg, kernel=kernel)
     if kernel:
         return evaluate_distributed(model, data, labels, dtype=cfg.dtype)
     fwd = model.module if isinstance(model, FlatBucketDDP) else model  # an OpsModel stays wrapped: its HIP kernels
@@ -419,6 +457,21 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
             load_optimizer_state(model, optimizer, cfg.resume, opt_step)
         if fused and opt_step != model.engine.optimizer_step():  # the schedule position (no sidecar to restore)
             model.engine.load_optimizer_state({**model.engine.optimizer_state(), "step": opt_step})
+    ema = None  # the generic engines' averager; the fused engine keeps its average in the optimiser pass
+    if cfg.ema_decay is not None:
+        from .utils.ema import ModelEma, ema_decay_at, load_ema_state, save_ema_state
+        if fused and model.engine.ema is None:
+            raise ValueError("--ema-decay is on but the fused trainer was built without it (train.engine_optimizer)")
+        if not fused:
+            ema = ModelEma(model, cfg.ema_decay, cfg.ema_warmup)
+        if cfg.resume:  # the average of the run being resumed (absent file: it restarts from the loaded parameters)
+            avg = load_ema_state(cfg.resume)
+            if avg is None:
+                print(f"warning: no {cfg.resume}.ema.pt: the EMA restarts from the loaded parameters", file=sys.stderr)
+            elif fused:
+                model.engine.load_ema_state_dict(avg)
+            else:
+                ema.load_state_dict(avg)
     last_lr = cfg.lr
     from contextlib import ExitStack
     from .utils.trace import trace_range as record_function  # torch.profiler + roctx ranges
@@ -473,6 +526,8 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                     loss.backward(_seed_grad(loss))
                 with record_function("optimizer"):
                     optimizer.step()
+                    if ema is not None:
+                        ema.update(opt_step + nsteps)
                 loss_sum += loss.item()
                 nsteps += 1
         global_step += nsteps
@@ -490,6 +545,10 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
         ev = run_eval(model, *eval_set, cfg) if eval_set is not None and (should_log(epoch) or epoch == cfg.epochs) \
             else None
         ev_rec = dict(eval_accuracy=ev.accuracy, eval_loss=ev.mean_loss, eval_images=ev.count) if ev else {}
+        ema_ev = run_eval(model, *eval_set, cfg, ema=True if fused else ema) \
+            if ev is not None and cfg.ema_decay is not None else None
+        if ema_ev is not None:
+            ev_rec.update(ema_eval_accuracy=ema_ev.accuracy, ema_eval_loss=ema_ev.mean_loss)
         mlog.write(epoch=epoch, loss=mean, steps=nsteps, seconds=dt, step_ms=1e3 * dt / max(nsteps, 1),
                    images_per_sec=nsteps * train_loader.batch_size / max(dt, 1e-9),
                    # exposed wait of the reduction kernel's gradient-segment exchanges, summed per step (xGMI)
@@ -497,6 +556,9 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                    engine=getattr(eng, "kind_name", cfg.engine if not fused else None),
                    lr=last_lr,  # the learning rate of the epoch's last step
                    augment=_augment_record(train_loader),
+                   # the decay of the epoch's last EMA update
+                   ema_decay=ema_decay_at(opt_step - 1, cfg.ema_decay, cfg.ema_warmup)
+                   if cfg.ema_decay is not None and opt_step > 0 else None,
                    dtype=cfg.dtype, fp32_mode=("3xbf16" if getattr(eng, "kind_name", "") == "sliced" else
                                                "fp32-mfma") if cfg.dtype == "fp32" and fused else None,
                    **ev_rec)
@@ -508,8 +570,12 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                     meta["opt_step"] = opt_step
                     save_optimizer_state(model, optimizer, ckpt, rank, opt_step)
                 save_checkpoint(model, ckpt, rank, meta=meta)
+                if cfg.ema_decay is not None and rank == 0:  # the averaged model, loadable like the checkpoint itself
+                    save_ema_state(model.engine.ema_state_dict() if fused else ema.state_dict(), ckpt, rank)
         if ev is not None and rank == 0:
             print(eval_line(epoch, ev.accuracy, ev.mean_loss), flush=True)
+            if ema_ev is not None:
+                print(eval_line_ema(epoch, ema_ev.accuracy, ema_ev.mean_loss), flush=True)
         if cfg.check_sync and epoch % cfg.check_sync == 0:
             assert_params_in_sync(unwrap(model))
     total = time.time() - start_time

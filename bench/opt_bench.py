@@ -1,14 +1,15 @@
 """Cost of the engine's optimiser pass: microseconds per training step of the plain fused engine (its own SGD inside
 the reduction kernel) against the same engine with ``momentum 0.9 + weight decay 5e-4 + cosine table`` (gradient
 reduced unapplied, then ``k_apply_opt``) and against that engine with the pass in its EMA form (``optimizer+ema``:
-decay 0.999, warm-up on), sliced engine, bf16 and fp32, batch 32, one GPU.
+decay 0.999, warm-up on) and in its AdamW form (``adamw``: betas (0.9, 0.999), weight decay 5e-2, the same table),
+sliced engine, bf16 and fp32, batch 32, one GPU.
 
 One process; the engines of a precision live side by side and are timed in interleaved repetitions (plain, optimiser,
-optimiser + EMA, plain, ...), so clock and thermal drift hit all alike.  Each repetition is `--steps` graph-replayed steps between two
+optimiser + EMA, AdamW, plain, ...), so clock and thermal drift hit all alike.  Each repetition is `--steps` graph-replayed steps between two
 HIP events recorded on the engine's stream; graphs are captured before the first timed repetition.  Reported: median
 and min / max over the repetitions, and the difference of the medians.
 
-    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32] [--no-ema]
+    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32] [--no-ema] [--no-adam]
 """
 from __future__ import annotations
 
@@ -56,6 +57,7 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--no-ema", action="store_true", help="time plain and optimizer only (A/B against older trees)")
+    ap.add_argument("--no-adam", action="store_true", help="leave the adamw engine out (A/B against older trees)")
     a = ap.parse_args(argv)
     from distributeddataparallel_cifar10_amd.data.synthetic import synthetic_cifar
     from distributeddataparallel_cifar10_amd.runtime.engine import OptimizerConfig
@@ -74,6 +76,9 @@ def main(argv=None):
         if not a.no_ema:
             ema = OptimizerConfig(momentum=0.9, weight_decay=5e-4, lr_table=table, ema_decay=0.999, ema_warmup=True)
             engines["optimizer+ema"] = _engine(dtype, a.batch, ema, data, labels, order)
+        if not a.no_adam:
+            adamw = OptimizerConfig(kind="adamw", betas=(0.9, 0.999), weight_decay=5e-2, lr_table=table)
+            engines["adamw"] = _engine(dtype, a.batch, adamw, data, labels, order)
         for eng in engines.values():
             _timed(eng, a.batch, a.warmup)
         us = {k: [] for k in engines}
@@ -90,6 +95,9 @@ def main(argv=None):
         if "optimizer+ema" in med:
             out[dtype].update(ema_us=round(med["optimizer+ema"], 2),
                               ema_delta_us=round(med["optimizer+ema"] - med["optimizer"], 2))
+        if "adamw" in med:
+            out[dtype].update(adamw_us=round(med["adamw"], 2),
+                              adamw_delta_us=round(med["adamw"] - med["optimizer"], 2))
         for k, v in us.items():
             print(f"{dtype} {k:13s} us/step: median {med[k]:.2f}  min {min(v):.2f}  max {max(v):.2f}  "
                   f"reps {' '.join(f'{x:.2f}' for x in v)}", flush=True)
@@ -98,6 +106,9 @@ def main(argv=None):
         if "optimizer+ema" in med:
             print(f"{dtype} EMA form costs {med['optimizer+ema'] - med['optimizer']:+.2f} us/step over optimizer "
                   f"({100 * (med['optimizer+ema'] / med['optimizer'] - 1):+.1f} %)", flush=True)
+        if "adamw" in med:
+            print(f"{dtype} AdamW form costs {med['adamw'] - med['optimizer']:+.2f} us/step over optimizer "
+                  f"({100 * (med['adamw'] / med['optimizer'] - 1):+.1f} %)", flush=True)
     print(json.dumps({"bench": "opt_bench", "engine": "sliced", "batch": a.batch, "steps": a.steps, "reps": a.reps,
                       **out}), flush=True)
 

@@ -290,6 +290,10 @@ static int enqueue_xgmi(Engine* e, const Ctx& cx, float* dst, int apply) {
 // The optimiser pass over the flat buffer (momentum, weight decay, the step's learning rate; derived weight copies;
 // CC4 base) -- in place of the step's own SGD when an optimiser is set.
 static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
+  if (e->opt.rule != dca::OPT_SGD) {
+    HIPCK(launch_apply_adam(e->bf, e->ema_on, e->opt.rule == dca::OPT_ADAMW, cx, e->optdev, e->st));
+    return 0;
+  }
   HIPCK(launch_apply_opt(e->bf, e->ema_on, cx, e->optdev, e->st));
   return 0;
 }
@@ -1049,9 +1053,11 @@ int dca_engine_set_optimizer(void* h, float* momentum_buf, float mu, float wd) {
   const bool on = momentum_buf != nullptr;
   if (on != e->opt_on) drop_graphs(e);
   e->opt_on = false;  // (on again below, once the device block is complete)
-  if (!on) {  // the EMA form goes with the pass
+  if (!on) {  // the EMA form and the Adam rule go with the pass
     e->ema_on = false;
     e->opt.ema = nullptr;
+    e->opt.rule = dca::OPT_SGD;
+    e->opt.v = nullptr;
     return 0;
   }
   if (e->optdev == nullptr) {  // first use: step 0, ticket 0, no table
@@ -1060,6 +1066,7 @@ int dca_engine_set_optimizer(void* h, float* momentum_buf, float mu, float wd) {
     e->opt.buf = momentum_buf;
     e->opt.mu = mu;
     e->opt.wd = wd;
+    e->opt.b1p = e->opt.b2p = 1.0;  // beta^0
     dca::OptDev* d = nullptr;
     HIPCK(hipMalloc((void**)&d, sizeof(dca::OptDev)));
     if (hipMemcpy(d, &e->opt, sizeof(dca::OptDev), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1141,8 +1148,61 @@ int dca_engine_set_ema(void* h, float* ema_buf, float decay, int warmup) {
   return 0;
 }
 
+// The Adam rule's running products beta1^step and beta2^step, recomputed for the device's step counter (after the
+// counter or the betas were set).  The stream must be idle.
+static int refresh_adam_products(Engine* e) {
+  int step = 0;
+  HIPCK(hipMemcpy(&step, &e->optdev->step, sizeof(int), hipMemcpyDeviceToHost));
+  const double prod[2] = {dca::adam_product(e->opt.beta1, step), dca::adam_product(e->opt.beta2, step)};
+  static_assert(offsetof(dca::OptDev, b2p) == offsetof(dca::OptDev, b1p) + sizeof(double), "b1p | b2p are one copy");
+  HIPCK(hipMemcpy(&e->optdev->b1p, prod, sizeof(prod), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Update rule of the optimiser pass: Adam (`decoupled` 0: torch.optim.Adam, the weight decay of
+// dca_engine_set_optimizer as an L2 term of the gradient) or AdamW (1: decay applied to the parameter), amsgrad off
+// (optimizer.hip, k_apply_adam).  `v_buf`: flat fp32 [FLAT_ALLOC] device buffer owned by the caller for the second
+// moment (zeroed or restored by the caller); the momentum buffer of dca_engine_set_optimizer is the first moment and
+// its `mu` is not used.  Needs the optimiser on; null switches back to SGD.  Changing the rule drops the captured
+// graphs (another kernel); new betas / eps on an engine already in that rule reach them as they are (device memory).
+// Synchronous.
+int dca_engine_set_adam(void* h, float* v_buf, double beta1, double beta2, double eps, int decoupled) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on) {
+    g_err = "set_adam: no optimiser set (dca_engine_set_optimizer first)";
+    return -1;
+  }
+  if (v_buf && (!(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.))) {
+    g_err = "set_adam: the betas must lie in [0, 1)";
+    return -1;
+  }
+  if (v_buf && (!(eps > 0.) || !((float)eps > 0.f) || !(eps < 3e38))) {
+    g_err = "set_adam: eps must be positive (and a normal fp32 value)";
+    return -1;
+  }
+  if (v_buf && ((uintptr_t)v_buf % 16)) {
+    g_err = "set_adam: the second-moment buffer must be 16-byte aligned";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  const int rule = !v_buf ? dca::OPT_SGD : decoupled ? dca::OPT_ADAMW : dca::OPT_ADAM;
+  if (rule != e->opt.rule) drop_graphs(e);
+  e->opt.v = v_buf;
+  e->opt.beta1 = v_buf ? beta1 : 0.;
+  e->opt.beta2 = v_buf ? beta2 : 0.;
+  e->opt.beta2f = (float)e->opt.beta2;
+  e->opt.omb1 = v_buf ? (float)(1. - beta1) : 0.f;
+  e->opt.omb2 = v_buf ? (float)(1. - beta2) : 0.f;
+  e->opt.eps = v_buf ? (float)eps : 0.f;
+  e->opt.rule = rule;
+  HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
+  if (rule != dca::OPT_SGD) return refresh_adam_products(e);
+  return 0;
+}
+
 // The optimiser pass's own step counter (it indexes the learning-rate table; unlike the loss step count it is never
-// reset by a loss read).  set = 0: *value <- counter; set = 1: counter <- *value (resume).  Synchronous.
+// reset by a loss read).  set = 0: *value <- counter; set = 1: counter <- *value (resume; under an Adam
+// rule the running products beta^step follow it).  Synchronous.
 int dca_engine_opt_step(void* h, int set, int* value) {
   Engine* e = (Engine*)h;
   if (!e->opt_on || !value) {
@@ -1156,6 +1216,7 @@ int dca_engine_opt_step(void* h, int set, int* value) {
       return -1;
     }
     HIPCK(hipMemcpy(&e->optdev->step, value, sizeof(int), hipMemcpyHostToDevice));
+    if (e->opt.rule != dca::OPT_SGD) return refresh_adam_products(e);
   } else {
     HIPCK(hipMemcpy(value, &e->optdev->step, sizeof(int), hipMemcpyDeviceToHost));
   }

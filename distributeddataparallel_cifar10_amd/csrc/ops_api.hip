@@ -589,6 +589,29 @@ int dca_ops_sgd(float* p, const float* g, float* buf, long n, float lr, float mu
   return 0;
 }
 
+// Adam (decoupled 0) / AdamW (1) over the flat fp32 slices p / g / m / v of n elements.  state: three device doubles
+// {steps taken, beta1^steps, beta2^steps} ({0, 1, 1} at the start); this update is step `steps taken + 1`.  advance
+// != 0: the state moves on one step after the update (the last -- or only -- update of an optimiser step).  n == 0
+// with advance: the state alone.
+int dca_ops_adam(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, double eps,
+                 float wd, int decoupled, double* state, int advance, void* stream) {
+  REQUIRE(state != nullptr, "adam: step state missing");
+  REQUIRE(n >= 0 && (n == 0 || (p && g && m && v)), "adam: buffer missing");
+  REQUIRE(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., "adam: the betas must lie in [0, 1)");
+  REQUIRE(eps > 0. && (float)eps > 0.f && eps < 3e38, "adam: eps must be positive");
+  REQUIRE(wd >= 0.f, "adam: weight decay must not be negative");
+  hipStream_t st = (hipStream_t)stream;
+  if (n > 0) {
+    auto* k = decoupled ? k_adam<true> : k_adam<false>;
+    // one float4 per thread up to 512 workgroups (two per CU), grid-stride beyond
+    hipLaunchKernelGGL(k, dim3(grid_for((n + 3) / 4, 256, 512)), dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2,
+                       (float)eps, wd, (const double*)state);
+  }
+  if (advance) hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, st, state, beta1, beta2);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
 // x (fp32 if is_f32 else bf16, n elements) -> q fp8 e4m3; amax_bits: device uint, zeroed here first.
 int dca_ops_quant_fp8(const void* x, int is_f32, long n, void* q, unsigned* amax_bits, void* stream) {
   hipStream_t st = (hipStream_t)stream;

@@ -1208,6 +1208,72 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, const float*
 __global__ void k_clear_flag(int* f) { *f = 0; }
 
 // ---------------------------------------------------------------------------------------------------------
+// Adam / AdamW over a flat fp32 slice p / g / m / v of any start alignment and length (torch.optim.Adam / AdamW,
+// amsgrad off; `decoupled`: AdamW).  The step state lives in device memory, so a captured whole-step graph replays
+// correctly: state = {steps taken, beta1^steps, beta2^steps} as three doubles, read by every update of a step and
+// advanced by k_adam_advance, launched once after the step's update(s).  Thread 0 forms the bias corrections in double
+// (one multiplication each from the running products, no pow); per element fp32 with IEEE sqrt and division:
+//   g' = g (+ wd * p: Adam);  p0 = p (AdamW: p - lr * wd * p);  m += omb1 * (g' - m);  v = beta2 * v + omb2 * g' * g'
+//   p  = p0 - ss * m / (sqrt(v) * c2 + eps),   ss = lr / (1 - beta1^t),  c2 = 1 / sqrt(1 - beta2^t),  t = steps + 1
+// The four slices share their offset from a common base, so they share their alignment: a scalar head up to the first
+// 16-byte boundary of p, float4 accesses over the body, a scalar tail.
+// ---------------------------------------------------------------------------------------------------------
+struct AdamK {
+  float ss, c2, lw, wd, omb1, omb2, beta2, eps;
+};
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamK& k) {
+  float p0 = p;
+  if constexpr (DECOUPLED) p0 = __builtin_fmaf(-k.lw, p0, p0);
+  else g = __builtin_fmaf(k.wd, p0, g);
+  m = __builtin_fmaf(k.omb1, g - m, m);
+  v = __builtin_fmaf(k.beta2, v, (k.omb2 * g) * g);
+  p = __builtin_fmaf(-k.ss, m / __builtin_fmaf(__builtin_sqrtf(v), k.c2, k.eps), p0);
+}
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, long n, float lr, double beta1, double beta2,
+                                              float eps, float wd, const double* __restrict__ state) {
+  __shared__ float s_ss, s_c2;
+  if (threadIdx.x == 0) {
+    s_ss = (float)((double)lr / (1.0 - state[1] * beta1));
+    s_c2 = (float)(1.0 / __builtin_sqrt(1.0 - state[2] * beta2));
+  }
+  __syncthreads();
+  const AdamK k{s_ss, s_c2, lr * wd, wd, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)beta2, eps};
+  long head = (long)((16 - ((uintptr_t)p & 15)) & 15) / 4;  // scalar elements in front of the first 16-byte boundary
+  const uintptr_t a = (uintptr_t)p & 15;  // slices of differently aligned buffers: everything on the scalar path
+  if (head > n || ((uintptr_t)g & 15) != a || ((uintptr_t)m & 15) != a || ((uintptr_t)v & 15) != a) head = n;
+  const long n4 = (n - head) >> 2, tail0 = head + 4 * n4;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  for (long i = gid; i < n4; i += stride) {
+    const long e = head + 4 * i;
+    f32x4 pp = *(const f32x4*)(p + e), mm = *(const f32x4*)(m + e), vv = *(const f32x4*)(v + e);
+    const f32x4 gg = *(const f32x4*)(g + e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pp[j], mj = mm[j], vj = vv[j];
+      adam_elem<DECOUPLED>(pj, gg[j], mj, vj, k);
+      pp[j] = pj, mm[j] = mj, vv[j] = vj;
+    }
+    *(f32x4*)(p + e) = pp;
+    *(f32x4*)(m + e) = mm;
+    *(f32x4*)(v + e) = vv;
+  }
+  // head [0, head) and tail [tail0, n), one element per thread (fewer than 8 together on the float4 path)
+  const long nedge = head + (n - tail0);
+  for (long i = gid; i < nedge; i += stride) {
+    const long e = i < head ? i : tail0 + (i - head);
+    adam_elem<DECOUPLED>(p[e], g[e], m[e], v[e], k);
+  }
+}
+__global__ void k_adam_advance(double* state, double beta1, double beta2) {
+  state[0] += 1.0;
+  state[1] *= beta1;
+  state[2] *= beta2;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // fp8 e4m3 (OCP) quantisation with a per-tensor scale computed on the device:
 //   amax = max |x|  (k_amax: per-block max, then atomicMax on the float bits -- non-negative floats order as
 //   unsigned ints);  q = sat(x * 448 / amax);  the GEMM multiplies by amax / 448 (inv scale) in its epilogue.

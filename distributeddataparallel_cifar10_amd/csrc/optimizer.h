@@ -16,12 +16,33 @@ struct OptDev {
                           // parameters in [0, OFF_RS), running_mean | running_var in [OFF_RS, OFF_RS + 64)), or null
   float ema_decay;        // in [0, 1)
   int ema_warmup;         // != 0: update k uses min(ema_decay, (1 + k) / (10 + k))
+  // Adam forms (k_apply_adam; dca_engine_set_adam): `buf` is the first moment m, `v` the second
+  float* v;               // second moment, flat fp32 [FLAT_ALLOC], or null
+  double beta1, beta2;    // as given (the running products below are their powers)
+  float beta2f;           // (float)beta2: v' = beta2f * v + omb2 * g'^2
+  float omb1, omb2;       // (float)(1 - beta1), (float)(1 - beta2), rounded once from the doubles
+  float eps;
+  int rule;               // OPT_SGD, OPT_ADAM (weight decay as an L2 term), OPT_ADAMW (decoupled)
+  // ---- everything above is set by the host (copied up to offsetof(OptDev, step)); below: device state ----
   int step;               // optimiser steps taken (device counter)
   unsigned ticket;        // workgroups that have finished reading `step` in the current launch
+  double b1p, b2p;        // beta1^step, beta2^step: running products, multiplied once per Adam launch by the workgroup
+                          // that advances `step`; the host sets them (adam_products) whenever it sets `step`
 };
+enum { OPT_SGD = 0, OPT_ADAM = 1, OPT_ADAMW = 2 };
+
+// beta^step as the device forms it: `step` successive double multiplications (so a restored step gives the bits an
+// uninterrupted run holds).
+inline double adam_product(double beta, int step) {
+  double b = 1.0;
+  for (int i = 0; i < step && b != 0.0; ++i) b *= beta;
+  return b;
+}
 
 // Enqueue k_apply_opt<bf, ema> on `st`: one pass over the flat buffer [0, OFF_RS); ema: the form that also updates
 // od->ema (which must then be set).  Returns the launch's hipError_t.
 hipError_t launch_apply_opt(bool bf, bool ema, const Ctx& cx, OptDev* od, hipStream_t st);
+// The same for the Adam forms, k_apply_adam<bf, ema, decoupled> (od->v set, od->rule OPT_ADAM / OPT_ADAMW).
+hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, const Ctx& cx, OptDev* od, hipStream_t st);
 
 }  // namespace dca

@@ -22,6 +22,8 @@
 // [OFF_RS, OFF_RS + 64) by the 64 threads that write the CC4 base.  d = ema_decay, or with warm-up
 // min(ema_decay, (1 + step) / (10 + step)), computed by thread 0 from the `step` it reads anyway.  The form without
 // EMA compiles to what the pass was before the EMA form existed.
+// The Adam forms (k_apply_adam<BF, EMA, DECOUPLED>; dca_engine_set_adam) are kernels of their own further down: the
+// SGD forms do not change with them.
 // A translation unit of its own (see optimizer.h); derive_param comes from netresdeep_kernels.hip.
 #include "netresdeep_kernels.hip"
 #include "optimizer.h"
@@ -99,6 +101,116 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
       __hip_atomic_store(&od->step, st < 0x7fffffff ? st + 1 : st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+
+// The Adam forms of the pass (dca_engine_set_adam): torch.optim.Adam (DECOUPLED false: weight decay as an L2 term of
+// the gradient) and AdamW (true: decay applied to the parameter), amsgrad off.  The same sweep, launch shape, learning
+// rate, step counter, derived copies, CC4 copy and EMA update as k_apply_opt; od->buf is the first moment m and od->v
+// the second.  Per element, fp32 with IEEE sqrt and division (t = step + 1):
+//   g' = g * inv_ws                    (Adam: g' = fmaf(wd, p, g * inv_ws))
+//   p0 = p                             (AdamW: p0 = fmaf(-(lr * wd), p, p))
+//   m  = fmaf(omb1, g' - m, m)         omb1 = (float)(1 - beta1)
+//   v  = fmaf(beta2f, v, (omb2 * g') * g')
+//   p  = fmaf(-ss, m / fmaf(sqrtf(v), c2, eps), p0)
+// with ss = lr / (1 - beta1^t) and c2 = 1 / sqrt(1 - beta2^t) formed in double by thread 0 from the running products
+// od->b1p = beta1^step, od->b2p = beta2^step (no pow: one multiplication each) and shared as floats.  The workgroup
+// that advances `step` also stores the new products.  The pads between tensors (g = p = m = v = 0) stay exactly 0:
+// m / (0 + eps) = 0.
+template <bool BF, bool EMA, bool DECOUPLED>
+__global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
+  __shared__ float s_lr, s_ss, s_c2;
+  __shared__ float s_ema;  // (EMA form only)
+  const int t = threadIdx.x, v = blockIdx.x * NT + t;
+  int st0 = 0;             // thread 0: the step and the products of this launch (t = step + 1)
+  double b1t = 0., b2t = 0.;
+  if (t == 0) {
+    const int st = __hip_atomic_load(&od->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int n = od->n_table;
+    st0 = st;
+    const float lr = n > 0 ? od->lr_table[st < n - 1 ? (st < 0 ? 0 : st) : n - 1] : od->lr_const;
+    b1t = __hip_atomic_load(&od->b1p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * od->beta1;
+    b2t = __hip_atomic_load(&od->b2p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * od->beta2;
+    s_lr = lr;
+    s_ss = (float)((double)lr / (1.0 - b1t));
+    s_c2 = (float)(1.0 / __builtin_sqrt(1.0 - b2t));
+    if constexpr (EMA) {
+      float d = od->ema_decay;
+      if (od->ema_warmup) {
+        const float k = (float)(st < 0 ? 0 : st);
+        d = fminf(d, (1.f + k) / (10.f + k));
+      }
+      s_ema = d;
+    }
+  }
+  const float wd = od->wd, omb1 = od->omb1, omb2 = od->omb2, beta2 = od->beta2f, eps = od->eps;
+  float* mbuf = od->buf;
+  float* vbuf = od->v;
+  float* ebuf = nullptr;
+  if constexpr (EMA) ebuf = od->ema;
+  __syncthreads();
+  const float ss = s_ss, c2 = s_c2;
+  if (v < OPT_V4) {
+    const int e0 = 4 * v;
+    const f32x4 g = *(const f32x4*)(cx.grads + e0);
+    f32x4 p = *(const f32x4*)(cx.params + e0);
+    f32x4 m = *(const f32x4*)(mbuf + e0);
+    f32x4 s = *(const f32x4*)(vbuf + e0);
+    f32x4 a;
+    if constexpr (EMA) a = *(const f32x4*)(ebuf + e0);
+    float lw = 0.f;
+    if constexpr (DECOUPLED) lw = s_lr * wd;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float gg = g[k] * cx.inv_ws;
+      float p0 = p[k];
+      if constexpr (DECOUPLED) p0 = __builtin_fmaf(-lw, p0, p0);
+      else gg = __builtin_fmaf(wd, p0, gg);
+      m[k] = __builtin_fmaf(omb1, gg - m[k], m[k]);
+      s[k] = __builtin_fmaf(beta2, s[k], (omb2 * gg) * gg);
+      p[k] = __builtin_fmaf(-ss, m[k] / __builtin_fmaf(__builtin_sqrtf(s[k]), c2, eps), p0);
+    }
+    *(f32x4*)(mbuf + e0) = m;
+    *(f32x4*)(vbuf + e0) = s;
+    *(f32x4*)(cx.params + e0) = p;
+    if constexpr (EMA) {
+      const float dk = s_ema;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = __builtin_fmaf(dk, a[k] - p[k], p[k]);
+      *(f32x4*)(ebuf + e0) = a;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) derive_param<BF>(cx, e0 + k, p[k]);
+  }
+  // CC4: rank 0's running statistics (the tail of the all-reduced buffer) become every rank's base
+  if (cx.ws > 1 && v < 64) cx.rs_base[v] = cx.grads[OFF_RS + v];
+  if constexpr (EMA) {  // the averaged running statistics, as in k_apply_opt
+    if (v < 64) {
+      float* er = ebuf + OFF_RS + v;
+      const float r = v < 32 ? cx.rm[v] : cx.rv[v - 32];
+      *er = __builtin_fmaf(s_ema, *er - r, r);
+    }
+  }
+  if (t == 0) {  // the last workgroup to arrive advances the step and the products (all have read them)
+    const unsigned prev = __hip_atomic_fetch_add(&od->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == gridDim.x - 1) {
+      __hip_atomic_store(&od->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (st0 < 0x7fffffff) {
+        __hip_atomic_store(&od->b1p, b1t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&od->b2p, b2t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&od->step, st0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
+hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, const Ctx& cx, OptDev* od, hipStream_t st) {
+  void (*k)(Ctx, OptDev*) = nullptr;
+#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D>
+  DCA_ADAM(false, false, false); DCA_ADAM(false, false, true); DCA_ADAM(false, true, false); DCA_ADAM(false, true, true);
+  DCA_ADAM(true, false, false); DCA_ADAM(true, false, true); DCA_ADAM(true, true, false); DCA_ADAM(true, true, true);
+#undef DCA_ADAM
+  hipLaunchKernelGGL(k, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
+  return hipGetLastError();
 }
 
 hipError_t launch_apply_opt(bool bf, bool ema, const Ctx& cx, OptDev* od, hipStream_t st) {

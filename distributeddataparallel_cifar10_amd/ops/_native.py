@@ -115,6 +115,9 @@ def _declare(lib):
                                     ctypes.c_long, c_int, c_int, c_int, c_void_p]
     lib.dca_ops_gather_cols.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]
     lib.dca_ops_sgd.argtypes = [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_void_p, c_void_p]
+    # p, g, m, v, n, lr, beta1, beta2, eps, wd, decoupled, state, advance, stream
+    lib.dca_ops_adam.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, ctypes.c_double,
+                                 ctypes.c_double, ctypes.c_double, c_float, c_int, c_void_p, c_int, c_void_p]
     lib.dca_ops_quant_fp8.argtypes = [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p]
     lib.dca_ops_fp8_alpha.argtypes = [c_void_p, c_void_p, c_float, c_void_p, c_void_p]
     lib.dca_ops_pack_weights.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]

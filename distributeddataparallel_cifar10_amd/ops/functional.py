@@ -1224,3 +1224,47 @@ def sgd_step_(p: torch.Tensor, g: torch.Tensor, lr: float, momentum: float = 0.0
         raise ValueError("sgd_step_: momentum needs a buffer")
     N.check(N.lib().dca_ops_sgd(N.ptr(p), N.ptr(g), N.ptr(buf), p.numel(), float(lr), float(momentum),
                                 float(weight_decay), N.ptr(first), N.stream(p.device)), "sgd")
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Adam / AdamW over flat fp32 buffers (torch.optim.Adam / AdamW, amsgrad off; utils/schedule.py adam_reference)
+# ------------------------------------------------------------------------------------------------------------
+def adam_state(device) -> torch.Tensor:
+    """A fresh step state of ``adam_step_``: three float64 words on `device`, {steps taken, beta1^steps, beta2^steps}
+    = {0, 1, 1}.  It lives in device memory so that a captured whole-step graph replays correctly."""
+    return torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=device)
+
+
+def adam_state_at(step: int, beta1: float, beta2: float, device) -> torch.Tensor:
+    """The step state after `step` steps, the running products formed as the device forms them (successive double
+    multiplications), so that a restored state holds the bits of an uninterrupted run."""
+    b1 = b2 = 1.0
+    for _ in range(int(step)):
+        b1 *= float(beta1)
+        b2 *= float(beta2)
+    return torch.tensor([float(int(step)), b1, b2], dtype=torch.float64, device=device)
+
+
+def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor, lr: float,
+               betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = True,
+               advance: bool = True) -> None:
+    """One Adam (``decoupled=False``) / AdamW update of the flat fp32 slice `p` in place from its gradient `g`, with
+    the moments `m` and `v` (zero at the start), as step ``state[0] + 1`` (``adam_state``).  ``advance=False`` leaves
+    the state where it is -- for all but the last of several slices updated in one optimiser step."""
+    _dev_check(p, g, m, v, state)
+    for t in (p, g, m, v):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+            raise TypeError("adam_step_: contiguous fp32 buffers of one length")
+    if state.dtype != torch.float64 or state.numel() != 3 or not state.is_contiguous():
+        raise TypeError("adam_step_: the step state is three float64 words (adam_state)")
+    from ..utils.schedule import check_adam
+    check_adam(betas[0], betas[1], eps, weight_decay)
+    N.check(N.lib().dca_ops_adam(N.ptr(p), N.ptr(g), N.ptr(m), N.ptr(v), p.numel(), float(lr), float(betas[0]),
+                                 float(betas[1]), float(eps), float(weight_decay), 1 if decoupled else 0, N.ptr(state),
+                                 1 if advance else 0, N.stream(p.device)), "adam")
+
+
+def adam_advance_(state: torch.Tensor, betas) -> None:
+    """Move an ``adam_step_`` state on one step without an update (after slices updated with ``advance=False``)."""
+    N.check(N.lib().dca_ops_adam(None, None, None, None, 0, 0.0, float(betas[0]), float(betas[1]), 1.0, 0.0, 0,
+                                 N.ptr(state), 1, N.stream(state.device)), "adam")

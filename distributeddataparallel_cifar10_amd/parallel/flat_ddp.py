@@ -408,3 +408,84 @@ class FlatSGD(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         _zero_flat(self.ddp.flat_grad)
+
+
+class FlatAdam(torch.optim.Optimizer):
+    """``optim.AdamW`` (``decoupled=True``, the default) or ``optim.Adam`` (``False``: weight decay as an L2 term of
+    the gradient) over the flat buffer, amsgrad off -- ``utils/schedule.py adam_reference`` is the rule.  On a GPU the
+    update is one HIP kernel (``ops/functional.py adam_step_``) and the step counter with its bias-correction products
+    lives in device memory, so a captured whole-step graph replays correctly; on the CPU it is torch ops in the order
+    of torch's own implementation.  ``overlap=True``: as for ``FlatSGD``, every gradient bucket is updated as soon as
+    it is reduced and ``step()`` only moves the step counter on."""
+
+    def __init__(self, ddp: FlatBucketDDP, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, decoupled: bool = True, overlap: bool = False):
+        from ..utils.schedule import check_adam
+        check_adam(betas[0], betas[1], eps, weight_decay)
+        if ddp.flat.dtype != torch.float32:
+            raise TypeError("FlatAdam: fp32 parameters")
+        super().__init__(list(ddp.module.parameters()),
+                         dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                              weight_decay=float(weight_decay)))
+        self.ddp = ddp
+        self.decoupled = bool(decoupled)
+        self.overlap = overlap
+        self.exp_avg = torch.zeros_like(ddp.flat)
+        self.exp_avg_sq = torch.zeros_like(ddp.flat)
+        self._t = 0  # CPU: optimiser steps taken
+        self._state = None  # GPU: the device step state of adam_step_
+        if ddp.flat.is_cuda:
+            from ..ops.functional import adam_state
+            self._state = adam_state(ddp.flat.device)
+        if overlap:
+            if ddp._fused_opt is not None:
+                raise ValueError("FlatBucketDDP already has a fused optimizer")
+            ddp._fused_opt = self
+
+    def steps_taken(self) -> int:
+        """Optimiser steps taken so far (GPU: reads the device counter, synchronises)."""
+        return int(self._state[0].item()) if self._state is not None else self._t
+
+    def set_steps_taken(self, step: int) -> None:
+        """Resume: the step counter (and with it the bias corrections) as after `step` steps."""
+        if self._state is not None:
+            from ..ops.functional import adam_state_at
+            b1, b2 = self.param_groups[0]["betas"]
+            self._state.copy_(adam_state_at(step, b1, b2, self._state.device))
+        self._t = int(step)
+
+    @torch.no_grad()
+    def _update_slice(self, s: int, e: int, advance: bool = False) -> None:
+        g = self.param_groups[0]
+        p, grad = self.ddp.flat[s:e], self.ddp.flat_grad[s:e]
+        m, v = self.exp_avg[s:e], self.exp_avg_sq[s:e]
+        (b1, b2), lr, eps, wd = g["betas"], g["lr"], g["eps"], g["weight_decay"]
+        if p.is_cuda:
+            from ..ops.functional import adam_step_
+            adam_step_(p, grad, m, v, self._state, lr, (b1, b2), eps, wd, decoupled=self.decoupled, advance=advance)
+            return
+        t = self._t + 1  # (the order of torch/optim/adam.py _single_tensor_adam)
+        if wd:
+            if self.decoupled:
+                p.mul_(1 - lr * wd)
+            else:
+                grad = grad.add(p, alpha=wd)
+        m.lerp_(grad, 1 - b1)
+        v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
+        denom = (v.sqrt() / (1 - b2 ** t) ** 0.5).add_(eps)
+        p.addcdiv_(m, denom, value=-(lr / (1 - b1 ** t)))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        if self.overlap:  # already applied bucket by bucket during the backward: only the counter moves
+            if self._state is not None:
+                from ..ops.functional import adam_advance_
+                adam_advance_(self._state, self.param_groups[0]["betas"])
+        else:
+            self._update_slice(0, self.ddp.flat.numel(), advance=True)
+        self._t += 1
+        return loss
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        _zero_flat(self.ddp.flat_grad)

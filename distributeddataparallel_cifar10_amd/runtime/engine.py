@@ -133,12 +133,42 @@ class OptimizerConfig:
     dampening 0 and decay on every tensor.  ``lr_table``: one learning rate per optimiser step (the last entry holds
     beyond its end; ``utils/schedule.py`` builds them); ``None``: the engine's constant ``lr``.  ``ema_decay``: the pass
     also keeps an exponential moving average of the parameters and the BatchNorm running statistics
-    (``utils/ema.py``; ``ema_warmup``: decay ``min(ema_decay, (1 + k) / (10 + k))`` at step k); ``None``: no average."""
+    (``utils/ema.py``; ``ema_warmup``: decay ``min(ema_decay, (1 + k) / (10 + k))`` at step k); ``None``: no average.
+    ``kind``: ``"sgd"`` (the above), or ``"adam"`` / ``"adamw"`` -- torch ``Adam`` / ``AdamW`` (amsgrad off) with
+    ``betas`` and ``eps``, the pass's Adam forms; ``weight_decay`` is then an L2 term of the gradient (``adam``) or
+    decoupled (``adamw``), and ``momentum`` must be 0 (``utils/schedule.py adam_reference`` is the rule)."""
     momentum: float = 0.0
     weight_decay: float = 0.0
     lr_table: Optional[Sequence[float]] = None
     ema_decay: Optional[float] = None
     ema_warmup: bool = False
+    kind: str = "sgd"
+    betas: Sequence[float] = (0.9, 0.999)
+    eps: float = 1e-8
+
+
+OPTIMIZER_KINDS = ("sgd", "adam", "adamw")
+
+
+def check_optimizer_config(opt: OptimizerConfig) -> None:
+    """ValueError for an ``OptimizerConfig`` no engine can run."""
+    if opt.kind not in OPTIMIZER_KINDS:
+        raise ValueError(f"optimizer kind must be one of {OPTIMIZER_KINDS}, got {opt.kind!r}")
+    if opt.momentum < 0 or opt.weight_decay < 0:
+        raise ValueError("momentum and weight_decay must not be negative")
+    if opt.kind != "sgd":
+        from ..utils.schedule import check_adam
+        if opt.momentum != 0:
+            raise ValueError(f"momentum belongs to SGD: optimizer kind {opt.kind!r} takes betas, not momentum")
+        if len(opt.betas) != 2:
+            raise ValueError("betas must be (beta1, beta2)")
+        check_adam(opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay)
+
+
+def optimizer_state_kind(state: dict) -> str:
+    """The optimiser kind an optimiser state (``optimizer_state()``, a ``.optim.pt`` sidecar) was written by; a state
+    without ``"kind"`` is SGD's."""
+    return str(state.get("kind", "sgd"))
 
 
 @dataclass
@@ -247,6 +277,7 @@ class NetResDeepEngine:
         self._n_indices = 0
         self.momentum = None  # flat fp32 momentum buffer (optimiser mode), laid out like `flat` and `grads`
         self.ema = None  # flat fp32 [FLAT_ALLOC] average (EMA on), laid out like `grads`: running stats at OFF_RS
+        self.exp_avg_sq = None  # flat fp32 second moment (an Adam kind; `momentum` is then the first moment)
         if cfg.optimizer is not None:
             self.set_optimizer(cfg.optimizer)
 
@@ -257,15 +288,25 @@ class NetResDeepEngine:
         if opt is None:
             native.check(self.lib.dca_engine_set_optimizer(self.h, None, 0.0, 0.0), "dca_engine_set_optimizer")
             self.cfg.optimizer = None
-            self.ema = None  # (the EMA form goes with the pass)
+            self.ema = None  # (the EMA form and the Adam rule go with the pass)
             return
-        if opt.momentum < 0 or opt.weight_decay < 0:
-            raise ValueError("momentum and weight_decay must not be negative")
+        check_optimizer_config(opt)
+        adam = opt.kind != "sgd"
         if self.momentum is None:
             self.momentum = torch.zeros(FLAT_ALLOC, dtype=torch.float32, device=self.device)
             torch.cuda.synchronize(self.device)
+        if adam and self.exp_avg_sq is None:
+            self.exp_avg_sq = torch.zeros(FLAT_ALLOC, dtype=torch.float32, device=self.device)
+            torch.cuda.synchronize(self.device)
         native.check(self.lib.dca_engine_set_optimizer(self.h, self.momentum.data_ptr(), float(opt.momentum),
                                                        float(opt.weight_decay)), "dca_engine_set_optimizer")
+        was_adam = self.cfg.optimizer is not None and self.cfg.optimizer.kind != "sgd"
+        if adam:
+            native.check(self.lib.dca_engine_set_adam(self.h, self.exp_avg_sq.data_ptr(), float(opt.betas[0]),
+                                                      float(opt.betas[1]), float(opt.eps),
+                                                      1 if opt.kind == "adamw" else 0), "dca_engine_set_adam")
+        elif was_adam:  # back to the SGD rule
+            native.check(self.lib.dca_engine_set_adam(self.h, None, 0.0, 0.0, 0.0, 0), "dca_engine_set_adam")
         self.cfg.optimizer = opt
         if opt.lr_table is not None:
             self.set_lr_table(opt.lr_table)
@@ -290,25 +331,40 @@ class NetResDeepEngine:
         return int(v.value)
 
     def optimizer_state(self) -> dict:
-        """``{"step": int, "momentum_buffer": {parameter name: tensor}}``; the tensors are views of the flat momentum
-        buffer through ``LAYOUT`` (clone them to keep a snapshot).  Synchronises."""
+        """``{"step": int, "momentum_buffer": {parameter name: tensor}}``, or with an Adam kind ``{"step", "kind",
+        "exp_avg": {...}, "exp_avg_sq": {...}}``; the tensors are views of the flat state buffers through ``LAYOUT``
+        (clone them to keep a snapshot).  Synchronises."""
         step = self.optimizer_step()
-        bufs = {name: self.momentum[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
-        return {"step": step, "momentum_buffer": bufs}
+
+        def views(flat):
+            return {name: flat[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
+        if self.cfg.optimizer.kind != "sgd":
+            return {"step": step, "kind": self.cfg.optimizer.kind, "exp_avg": views(self.momentum),
+                    "exp_avg_sq": views(self.exp_avg_sq)}
+        return {"step": step, "momentum_buffer": views(self.momentum)}
 
     def load_optimizer_state(self, state: dict) -> None:
-        """Restore ``optimizer_state()`` output (tensors on any device)."""
+        """Restore ``optimizer_state()`` output (tensors on any device).  A state of another kind than the engine's
+        optimiser is refused."""
         self._need_optimizer()
-        bufs = state["momentum_buffer"]
-        if set(bufs) != set(LAYOUT):
-            raise ValueError(f"momentum buffers must cover exactly {sorted(LAYOUT)}")
+        kind, theirs = self.cfg.optimizer.kind, optimizer_state_kind(state)
+        if kind != theirs:
+            raise ValueError(f"optimiser state of kind {theirs!r} cannot be loaded into an engine whose optimiser is "
+                             f"{kind!r}")
+        pairs = [("momentum_buffer", self.momentum)] if kind == "sgd" else \
+            [("exp_avg", self.momentum), ("exp_avg_sq", self.exp_avg_sq)]
+        for key, _ in pairs:
+            if set(state[key]) != set(LAYOUT):
+                raise ValueError(f"{key} must cover exactly {sorted(LAYOUT)}")
+            for name, (off, shape) in LAYOUT.items():
+                if tuple(state[key][name].shape) != shape:
+                    raise ValueError(f"{key} {name}: expected shape {shape}, got {tuple(state[key][name].shape)}")
         self.sync()
         with torch.no_grad():
-            for name, (off, shape) in LAYOUT.items():
-                t = bufs[name]
-                if tuple(t.shape) != shape:
-                    raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-                self.momentum[off:off + t.numel()].copy_(t.detach().to(self.device, torch.float32).reshape(-1))
+            for key, flat in pairs:
+                for name, (off, shape) in LAYOUT.items():
+                    t = state[key][name]
+                    flat[off:off + t.numel()].copy_(t.detach().to(self.device, torch.float32).reshape(-1))
         torch.cuda.synchronize(self.device)
         v = ctypes.c_int(int(state["step"]))
         native.check(self.lib.dca_engine_opt_step(self.h, 1, ctypes.byref(v)), "dca_engine_opt_step")

@@ -86,6 +86,8 @@ def _declare(lib):
     lib.dca_engine_set_lr_table.argtypes = [c_void_p, c_void_p, c_int]
     lib.dca_engine_opt_step.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]
     lib.dca_engine_set_ema.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_int]  # handle, buffer, decay, warm-up
+    # handle, second-moment buffer, beta1, beta2, eps, decoupled
+    lib.dca_engine_set_adam.argtypes = [c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int]
     lib.dca_eval_netresdeep.argtypes = [c_void_p, c_void_p]  # DcaEvalArgs*, hipStream_t (runtime/evaluate.py)
     # csrc/augment.hip (data/augment.py): src, dst, ids, n, n_rows, seed, epoch, pad, flip, hipStream_t; no engine
     # handle, and an error string of its own

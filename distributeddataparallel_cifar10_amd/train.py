@@ -18,7 +18,9 @@ fault injection (``fail_at_step``), process-group timeout, set_epoch reshuffling
 momentum / weight decay / a per-step learning-rate schedule (``optimizer_active``; one table drives every engine),
 ``--augment`` (per-epoch random crop + flip of the training images, ``data/augment.py``), ``--ema-decay`` (an
 exponential moving average of the weights, ``utils/ema.py``: kept by the fused engine's optimiser pass on the device, by
-``ModelEma`` on the other engines; evaluated beside the live model and saved as ``<checkpoint>.ema.pt``).
+``ModelEma`` on the other engines; evaluated beside the live model and saved as ``<checkpoint>.ema.pt``),
+``--optimizer adam`` / ``adamw`` (the Adam forms of the fused engine's optimiser pass, ``FlatAdam`` on ``ops``, torch's
+own on ``torch`` and the CPU; ``utils/schedule.py adam_reference`` is the rule).
 """
 from __future__ import annotations
 
@@ -81,6 +83,10 @@ class TrainConfig:
     augment_flip: bool = True
     ema_decay: Optional[float] = None  # None: no average; D in [0, 1): EMA of the weights (see optimizer_active())
     ema_warmup: bool = False         # decay min(D, (1 + k) / (10 + k)) at optimiser step k
+    optimizer: str = "sgd"           # sgd | adam (weight_decay as an L2 term) | adamw (weight_decay decoupled)
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.999
+    adam_eps: float = 1e-8
     extra: dict = field(default_factory=dict)
 
 
@@ -129,7 +135,15 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--eval-only", action="store_true",
                     help="load --resume, evaluate as --eval does, print the result and exit without training")
     ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (dampening 0); default 0: plain SGD")
-    ap.add_argument("--weight-decay", type=float, default=0.0, help="L2 weight decay on every parameter tensor")
+    ap.add_argument("--weight-decay", type=float, default=0.0,
+                    help="weight decay on every parameter tensor: an L2 term of the gradient (--optimizer sgd, adam) "
+                         "or decoupled (adamw)")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adamw"],
+                    help="update rule: SGD (default), or torch's Adam / AdamW (amsgrad off) with --adam-beta1, "
+                         "--adam-beta2, --adam-eps; --momentum belongs to sgd")
+    ap.add_argument("--adam-beta1", type=float, default=0.9, help="Adam / AdamW: first-moment decay, in [0, 1)")
+    ap.add_argument("--adam-beta2", type=float, default=0.999, help="Adam / AdamW: second-moment decay, in [0, 1)")
+    ap.add_argument("--adam-eps", type=float, default=1e-8, help="Adam / AdamW: the denominator's epsilon, > 0")
     ap.add_argument("--lr-schedule", default=None, choices=["constant", "step", "cosine"],
                     help="per-step learning-rate schedule over epochs x steps-per-epoch steps (default: constant --lr)")
     ap.add_argument("--lr-warmup-steps", type=int, default=0, help="linear warm-up over the first N steps")
@@ -173,7 +187,24 @@ def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConf
                        augment_pad=getattr(a, "augment_pad", 4),
                        augment_flip=not getattr(a, "augment_no_flip", False),
                        ema_decay=_ema_decay_arg(getattr(a, "ema_decay", None)),
-                       ema_warmup=bool(getattr(a, "ema_warmup", False)))
+                       ema_warmup=bool(getattr(a, "ema_warmup", False)), **_optimizer_args(a))
+
+
+def _optimizer_args(a: argparse.Namespace) -> dict:
+    """The ``--optimizer`` / ``--adam-*`` fields of ``TrainConfig``; values no optimiser takes exit here."""
+    kind = getattr(a, "optimizer", "sgd")
+    out = dict(optimizer=kind, adam_beta1=getattr(a, "adam_beta1", 0.9), adam_beta2=getattr(a, "adam_beta2", 0.999),
+               adam_eps=getattr(a, "adam_eps", 1e-8))
+    if kind != "sgd":
+        if getattr(a, "momentum", 0.0):
+            raise SystemExit(f"--momentum belongs to --optimizer sgd; --optimizer {kind} takes --adam-beta1 / "
+                             f"--adam-beta2")
+        from .utils.schedule import check_adam
+        try:
+            check_adam(out["adam_beta1"], out["adam_beta2"], out["adam_eps"], getattr(a, "weight_decay", 0.0))
+        except ValueError as ex:
+            raise SystemExit(f"--optimizer {kind}: {ex}")
+    return out
 
 
 def _ema_decay_arg(decay):
@@ -186,9 +217,10 @@ def optimizer_active(cfg: TrainConfig) -> bool:
     """Whether any optimiser option beyond the reference's SGD(lr) is on.  Off (the default): the fused engine runs
     its own fused SGD (``optimizer=None``) and the other engines build FlatSGD(model, lr) / torch.optim.SGD(lr).
     ``--ema-decay`` alone turns it on too: the fused engine keeps the average in its optimiser pass, so it then takes
-    the split step form (with a constant table if no schedule is given)."""
+    the split step form (with a constant table if no schedule is given).  So does ``--optimizer adam`` / ``adamw``:
+    the Adam rule is a form of that pass."""
     return bool(cfg.momentum or cfg.weight_decay or cfg.lr_schedule is not None or cfg.lr_warmup_steps
-                or cfg.ema_decay is not None)
+                or cfg.ema_decay is not None or cfg.optimizer != "sgd")
 
 
 def steps_per_epoch_of(cfg: TrainConfig, n_batches: int) -> int:
@@ -216,7 +248,8 @@ def engine_optimizer(cfg: TrainConfig, n_batches: int):
         return None
     from .runtime.engine import OptimizerConfig
     return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table,
-                           ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
+                           ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup, kind=cfg.optimizer,
+                           betas=(cfg.adam_beta1, cfg.adam_beta2), eps=cfg.adam_eps)
 
 
 def augment_config(cfg: TrainConfig):
@@ -244,58 +277,120 @@ def optim_path(checkpoint_path: str) -> str:
     return f"{checkpoint_path}.optim.pt"
 
 
+def make_adam(model, cfg: TrainConfig):
+    """The generic engines' optimiser of ``--optimizer adam`` / ``adamw``: ``FlatAdam`` over a ``FlatBucketDDP``'s flat
+    buffer (the ``ops`` engine's HIP kernel on a GPU), else torch's own ``Adam`` / ``AdamW``."""
+    from .parallel.flat_ddp import FlatAdam, FlatBucketDDP
+    betas = (cfg.adam_beta1, cfg.adam_beta2)
+    if isinstance(model, FlatBucketDDP):
+        return FlatAdam(model, cfg.lr, betas=betas, eps=cfg.adam_eps, weight_decay=cfg.weight_decay,
+                        decoupled=cfg.optimizer == "adamw")
+    cls = torch.optim.AdamW if cfg.optimizer == "adamw" else torch.optim.Adam
+    return cls(model.parameters(), lr=cfg.lr, betas=betas, eps=cfg.adam_eps, weight_decay=cfg.weight_decay)
+
+
+def _flat_views(model, flat, buf) -> dict:
+    """{parameter name: view of `buf`}, `buf` laid out like the flat parameter buffer `flat`."""
+    out = {}
+    for name, p in unwrap(model).named_parameters():
+        off = (p.data_ptr() - flat.data_ptr()) // flat.element_size()
+        out[name] = buf[off:off + p.numel()].view(p.shape)
+    return out
+
+
+def _state_buffers(model, optimizer, key: str) -> dict:
+    """{parameter name: the optimiser's per-parameter state tensor `key`} of a torch optimiser (tensors absent before
+    the first step)."""
+    return {name: optimizer.state[p][key] for name, p in unwrap(model).named_parameters()
+            if optimizer.state.get(p, {}).get(key) is not None}
+
+
 def _momentum_buffers(model, optimizer) -> dict:
     """{parameter name: momentum buffer} of the generic engines' optimiser (tensors absent before the first step)."""
     from .parallel.flat_ddp import FlatSGD
-    named = dict(unwrap(model).named_parameters())
     if isinstance(optimizer, FlatSGD):
-        buf, flat = optimizer._buf, optimizer.ddp.flat
-        if buf is None:
+        if optimizer._buf is None:
             return {}
-        out = {}
-        for name, p in named.items():
-            off = (p.data_ptr() - flat.data_ptr()) // flat.element_size()
-            out[name] = buf[off:off + p.numel()].view(p.shape)
-        return out
-    return {name: optimizer.state[p]["momentum_buffer"] for name, p in named.items()
-            if optimizer.state.get(p, {}).get("momentum_buffer") is not None}
+        return _flat_views(model, optimizer.ddp.flat, optimizer._buf)
+    return _state_buffers(model, optimizer, "momentum_buffer")
 
 
-def save_optimizer_state(model, optimizer, path: str, rank: int, step: int) -> None:
-    """Rank 0 writes ``<checkpoint>.optim.pt``: ``{"step", "momentum_buffer": {name: CPU tensor}}`` (atomically)."""
+def _adam_moments(model, optimizer) -> tuple:
+    """({parameter name: exp_avg}, {parameter name: exp_avg_sq}) of the generic engines' Adam optimiser."""
+    from .parallel.flat_ddp import FlatAdam
+    if isinstance(optimizer, FlatAdam):
+        flat = optimizer.ddp.flat
+        return _flat_views(model, flat, optimizer.exp_avg), _flat_views(model, flat, optimizer.exp_avg_sq)
+    return _state_buffers(model, optimizer, "exp_avg"), _state_buffers(model, optimizer, "exp_avg_sq")
+
+
+def save_optimizer_state(model, optimizer, path: str, rank: int, step: int, kind: str = "sgd") -> None:
+    """Rank 0 writes ``<checkpoint>.optim.pt`` (atomically): ``{"step", "momentum_buffer": {name: CPU tensor}}``, or
+    with `kind` ``adam`` / ``adamw`` ``{"step", "kind", "exp_avg": {...}, "exp_avg_sq": {...}}``."""
     from .parallel.ddp import FusedDDPTrainer
     if rank != 0:
         return
+
+    def cpu(bufs):
+        return {k: v.detach().to("cpu", copy=True) for k, v in bufs.items()}
     extra = {}
     if isinstance(model, FusedDDPTrainer):
-        bufs = model.engine.optimizer_state()["momentum_buffer"]
+        st = model.engine.optimizer_state()
         extra["engine"] = model.engine.step_state()  # the step kernels' carried BN shifts (bitwise resume)
+    elif kind != "sgd":
+        st = dict(zip(("exp_avg", "exp_avg_sq"), _adam_moments(model, optimizer)))
     else:
-        bufs = _momentum_buffers(model, optimizer)
-    state = {"step": int(step), "momentum_buffer": {k: v.detach().to("cpu", copy=True) for k, v in bufs.items()},
-             **extra}
+        st = {"momentum_buffer": _momentum_buffers(model, optimizer)}
+    if kind != "sgd":
+        state = {"step": int(step), "kind": kind, "exp_avg": cpu(st["exp_avg"]), "exp_avg_sq": cpu(st["exp_avg_sq"]),
+                 **extra}
+    else:
+        state = {"step": int(step), "momentum_buffer": cpu(st["momentum_buffer"]), **extra}
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = f"{optim_path(path)}.tmp.{os.getpid()}"
     torch.save(state, tmp)
     os.replace(tmp, optim_path(path))
 
 
-def load_optimizer_state(model, optimizer, path: str, step: int) -> bool:
-    """Restore ``<checkpoint>.optim.pt`` if present (momentum buffers; the fused engine's step counter <- `step`)."""
+def load_optimizer_state(model, optimizer, path: str, step: int, kind: str = "sgd") -> bool:
+    """Restore ``<checkpoint>.optim.pt`` if present (momentum buffers or Adam moments; the step counter <- `step`).
+    A sidecar written by another optimiser kind than `kind` ends the run (one without ``"kind"`` is SGD's)."""
     from .parallel.ddp import FusedDDPTrainer
-    from .parallel.flat_ddp import FlatSGD
+    from .parallel.flat_ddp import FlatAdam, FlatSGD
+    from .runtime.engine import optimizer_state_kind
     if not os.path.exists(optim_path(path)):
         return False
     state = torch.load(optim_path(path), map_location="cpu", weights_only=True)
-    bufs = state["momentum_buffer"]
+    theirs = optimizer_state_kind(state)
+    if theirs != kind:
+        raise SystemExit(f"--resume: {optim_path(path)} holds the state of --optimizer {theirs}, this run uses "
+                         f"--optimizer {kind}; resume with --optimizer {theirs}, or remove the file to restart the "
+                         f"optimiser state")
     if isinstance(model, FusedDDPTrainer):
-        model.engine.load_optimizer_state({"step": int(step), "momentum_buffer": bufs})
+        model.engine.load_optimizer_state({**{k: v for k, v in state.items() if k != "engine"}, "step": int(step)})
         if "engine" in state:
             model.engine.load_step_state(state["engine"])
         return True
+    named = dict(unwrap(model).named_parameters())
+    if kind != "sgd":
+        m, v = state["exp_avg"], state["exp_avg_sq"]
+        with torch.no_grad():
+            if isinstance(optimizer, FlatAdam):
+                flat = optimizer.ddp.flat
+                for bufs, dst in ((m, optimizer.exp_avg), (v, optimizer.exp_avg_sq)):
+                    if bufs:
+                        for name, view in _flat_views(model, flat, dst).items():
+                            view.copy_(bufs[name])
+                optimizer.set_steps_taken(int(step))
+            elif m:
+                for name, p in named.items():
+                    optimizer.state[p] = {"step": torch.tensor(float(step)),
+                                          "exp_avg": m[name].to(p.device, p.dtype).clone(),
+                                          "exp_avg_sq": v[name].to(p.device, p.dtype).clone()}
+        return True
+    bufs = state["momentum_buffer"]
     if not bufs:
         return True
-    named = dict(unwrap(model).named_parameters())
     with torch.no_grad():
         if isinstance(optimizer, FlatSGD):
             flat = optimizer.ddp.flat
@@ -442,6 +537,8 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
             if table is None:
                 optimizer = FlatSGD(model, cfg.lr) if isinstance(model, FlatBucketDDP) else \
                     torch.optim.SGD(model.parameters(), lr=cfg.lr)
+            elif cfg.optimizer != "sgd":
+                optimizer = make_adam(model, cfg)
             else:
                 optimizer = FlatSGD(model, cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay) \
                     if isinstance(model, FlatBucketDDP) else \
@@ -454,7 +551,7 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                              "(train.engine_optimizer)")
         opt_step = int(cfg.extra.get("opt_step", global_step))
         if cfg.resume:  # momentum buffers of the run being resumed (absent file: they start at zero)
-            load_optimizer_state(model, optimizer, cfg.resume, opt_step)
+            load_optimizer_state(model, optimizer, cfg.resume, opt_step, cfg.optimizer)
         if fused and opt_step != model.engine.optimizer_step():  # the schedule position (no sidecar to restore)
             model.engine.load_optimizer_state({**model.engine.optimizer_state(), "step": opt_step})
     ema = None  # the generic engines' averager; the fused engine keeps its average in the optimiser pass
@@ -568,7 +665,7 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                 meta = {"epoch": epoch, "step": global_step}
                 if table is not None:  # optimiser sidecar: momentum buffers + the schedule position
                     meta["opt_step"] = opt_step
-                    save_optimizer_state(model, optimizer, ckpt, rank, opt_step)
+                    save_optimizer_state(model, optimizer, ckpt, rank, opt_step, cfg.optimizer)
                 save_checkpoint(model, ckpt, rank, meta=meta)
                 if cfg.ema_decay is not None and rank == 0:  # the averaged model, loadable like the checkpoint itself
                     save_ema_state(model.engine.ema_state_dict() if fused else ema.state_dict(), ckpt, rank)

@@ -71,6 +71,48 @@ def sgd_reference(p, g, buf, lr: float, mu: float, wd: float, inv_ws: float = 1.
     return p64 - float(lr) * nb, nb
 
 
+ADAM_KINDS = ("adam", "adamw")
+
+
+def check_adam(beta1: float, beta2: float, eps: float, wd: float = 0.0) -> None:
+    """The value ranges of the Adam rule (the ones every layer enforces): ValueError outside them."""
+    if not (0.0 <= float(beta1) < 1.0) or not (0.0 <= float(beta2) < 1.0):
+        raise ValueError(f"Adam betas must lie in [0, 1), got ({beta1}, {beta2})")
+    if not (float(eps) > 0.0) or not math.isfinite(float(eps)):
+        raise ValueError(f"Adam eps must be positive, got {eps}")
+    if not (float(wd) >= 0.0):
+        raise ValueError(f"weight decay must not be negative, got {wd}")
+
+
+def adam_reference(p, g, m, v, t: int, lr: float, beta1: float, beta2: float, eps: float, wd: float,
+                   decoupled: bool, inv_ws: float = 1.0):
+    """One update of Adam (``decoupled=False``: weight decay as an L2 term of the gradient) or AdamW (``True``: decay
+    applied to the parameter) in float64 -- torch ``optim.Adam`` / ``AdamW`` with ``amsgrad=False``, the oracle of the
+    Adam forms of ``k_apply_opt`` and of ``k_adam``.  `t` is the 1-based step:
+
+        g' = g * inv_ws  (+ wd * p: Adam);   p0 = p * (1 - lr * wd)  (AdamW; else p)
+        m' = m + (1 - beta1) * (g' - m);     v' = beta2 * v + (1 - beta2) * g' * g'
+        p' = p0 - (lr / (1 - beta1^t)) * m' / (sqrt(v') / sqrt(1 - beta2^t) + eps)
+
+    `m` and `v` start at zero.  Takes arrays or tensors; returns ``(p', m', v')`` as float64 numpy arrays."""
+    check_adam(beta1, beta2, eps, wd)
+    t = int(t)
+    if t < 1:
+        raise ValueError("the Adam step t is 1-based")
+    p64, g64, m64, v64 = (_f64(x) for x in (p, g, m, v))
+    b1, b2, lr, wd = float(beta1), float(beta2), float(lr), float(wd)
+    gg = g64 * float(inv_ws)
+    if decoupled:
+        p0 = p64 * (1.0 - lr * wd)
+    else:
+        gg = gg + wd * p64
+        p0 = p64
+    nm = m64 + (1.0 - b1) * (gg - m64)
+    nv = b2 * v64 + (1.0 - b2) * gg * gg
+    denom = np.sqrt(nv) / math.sqrt(1.0 - b2 ** t) + float(eps)
+    return p0 - (lr / (1.0 - b1 ** t)) * nm / denom, nm, nv
+
+
 def _f64(x) -> np.ndarray:
     if hasattr(x, "detach"):
         x = x.detach().cpu().double().numpy()

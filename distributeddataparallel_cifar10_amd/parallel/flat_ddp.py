@@ -38,6 +38,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from ..utils.checkpoint import unwrap
+
 
 def _zero_flat(t: torch.Tensor) -> None:
     """Zero a flat (contiguous) gradient buffer: on a GPU one runtime fill on the current stream (no ATen kernel in
@@ -201,6 +203,8 @@ class FlatBucketDDP(nn.Module):
             for b in self._loose_buffers:
                 dist.broadcast(b, 0, group=self.process_group)
 
+    sync_buffers = _broadcast_buffers_now  # public: rank 0's buffers now (evaluation outside a forward)
+
     def _make_hook(self, p):
         ready = self._make_ready(p)
 
@@ -329,6 +333,15 @@ class FlatBucketDDP(nn.Module):
             self._comm_events = []
         return tot, n
 
+    def named_views(self, buf: torch.Tensor) -> dict:
+        """{parameter name: view of `buf`}, `buf` laid out like ``flat`` (a momentum buffer, an Adam moment, an
+        average of the parameters); the names are the innermost module's, as in its ``state_dict``."""
+        base, esz, out = self.flat.data_ptr(), self.flat.element_size(), {}
+        for name, p in unwrap(self.module).named_parameters():
+            off = (p.data_ptr() - base) // esz
+            out[name] = buf[off:off + p.numel()].view(p.shape)
+        return out
+
     def check_comm(self) -> None:
         """Raise if the xGMI all-reduce recorded a peer timeout (synchronous; call at log points)."""
         if self.xgmi is not None:
@@ -356,7 +369,8 @@ class FlatSGD(torch.optim.Optimizer):
                  overlap: bool = False):
         super().__init__(list(ddp.module.parameters()), dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
         self.ddp = ddp
-        self._buf = None
+        self._buf = None    # the flat momentum buffer; None before the first momentum step
+        self._first = None  # GPU: the HIP kernel's "buffer not initialised yet" flag (an int32 on the device)
         self.overlap = overlap
         if overlap:
             if ddp._fused_opt is not None:
@@ -392,7 +406,7 @@ class FlatSGD(torch.optim.Optimizer):
                 self._buf = torch.empty_like(self.ddp.flat)
                 self._first = torch.ones(1, dtype=torch.int32, device=self.ddp.flat.device)
             sgd_step_(self.ddp.flat, self.ddp.flat_grad, g["lr"], g["momentum"], g["weight_decay"], buf=self._buf,
-                      first=getattr(self, "_first", None))
+                      first=self._first)
             return loss
         grad = self.ddp.flat_grad
         if g["weight_decay"]:
@@ -408,6 +422,24 @@ class FlatSGD(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         _zero_flat(self.ddp.flat_grad)
+
+    def sidecar_state(self) -> dict:
+        """``{"momentum_buffer": {parameter name: view of the flat buffer}}`` -- the optimiser sidecar's shape; empty
+        before the first momentum step."""
+        return {"momentum_buffer": {} if self._buf is None else self.ddp.named_views(self._buf)}
+
+    @torch.no_grad()
+    def load_sidecar_state(self, state: dict, step: int = 0) -> None:
+        """Restore ``sidecar_state()`` output (tensors on any device); an empty one leaves the optimiser as it is."""
+        bufs = state["momentum_buffer"]
+        if not bufs:
+            return
+        flat = self.ddp.flat
+        self._buf = torch.zeros_like(flat)
+        if flat.is_cuda:  # the buffer is initialised now
+            self._first = torch.zeros(1, dtype=torch.int32, device=flat.device)
+        for name, view in self.ddp.named_views(self._buf).items():
+            view.copy_(bufs[name])
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -489,3 +521,18 @@ class FlatAdam(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         _zero_flat(self.ddp.flat_grad)
+
+    def sidecar_state(self) -> dict:
+        """``{"kind", "exp_avg": {parameter name: view}, "exp_avg_sq": {...}}`` -- the optimiser sidecar's shape."""
+        return {"kind": "adamw" if self.decoupled else "adam", "exp_avg": self.ddp.named_views(self.exp_avg),
+                "exp_avg_sq": self.ddp.named_views(self.exp_avg_sq)}
+
+    @torch.no_grad()
+    def load_sidecar_state(self, state: dict, step: int = 0) -> None:
+        """Restore ``sidecar_state()`` output (tensors on any device; empty moments stay as they are) and the step
+        counter, with its bias corrections, as after `step` steps."""
+        for key, dst in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+            if state[key]:
+                for name, view in self.ddp.named_views(dst).items():
+                    view.copy_(state[key][name])
+        self.set_steps_taken(int(step))

@@ -335,13 +335,15 @@ class NetResDeepEngine:
         "exp_avg": {...}, "exp_avg_sq": {...}}``; the tensors are views of the flat state buffers through ``LAYOUT``
         (clone them to keep a snapshot).  Synchronises."""
         step = self.optimizer_step()
-
-        def views(flat):
-            return {name: flat[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
         if self.cfg.optimizer.kind != "sgd":
-            return {"step": step, "kind": self.cfg.optimizer.kind, "exp_avg": views(self.momentum),
-                    "exp_avg_sq": views(self.exp_avg_sq)}
-        return {"step": step, "momentum_buffer": views(self.momentum)}
+            return {"step": step, "kind": self.cfg.optimizer.kind, "exp_avg": self._views(self.momentum),
+                    "exp_avg_sq": self._views(self.exp_avg_sq)}
+        return {"step": step, "momentum_buffer": self._views(self.momentum)}
+
+    @staticmethod
+    def _views(flat: torch.Tensor) -> dict:
+        """{parameter name: view of `flat`} through ``LAYOUT``, `flat` laid out like the flat parameter buffer."""
+        return {name: flat[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
 
     def load_optimizer_state(self, state: dict) -> None:
         """Restore ``optimizer_state()`` output (tensors on any device).  A state of another kind than the engine's
@@ -356,15 +358,14 @@ class NetResDeepEngine:
         for key, _ in pairs:
             if set(state[key]) != set(LAYOUT):
                 raise ValueError(f"{key} must cover exactly {sorted(LAYOUT)}")
-            for name, (off, shape) in LAYOUT.items():
+            for name, (_, shape) in LAYOUT.items():
                 if tuple(state[key][name].shape) != shape:
                     raise ValueError(f"{key} {name}: expected shape {shape}, got {tuple(state[key][name].shape)}")
         self.sync()
         with torch.no_grad():
             for key, flat in pairs:
-                for name, (off, shape) in LAYOUT.items():
-                    t = state[key][name]
-                    flat[off:off + t.numel()].copy_(t.detach().to(self.device, torch.float32).reshape(-1))
+                for name, view in self._views(flat).items():
+                    view.copy_(state[key][name].detach().to(self.device, torch.float32))
         torch.cuda.synchronize(self.device)
         v = ctypes.c_int(int(state["step"]))
         native.check(self.lib.dca_engine_opt_step(self.h, 1, ctypes.byref(v)), "dca_engine_opt_step")
@@ -414,7 +415,7 @@ class NetResDeepEngine:
     def _ema_views(self) -> dict:
         """{unique tensor name: view of the averaged buffer} -- the nine parameters through ``LAYOUT`` and the two
         running statistics at ``OFF_RS``."""
-        out = {name: self.ema[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in LAYOUT.items()}
+        out = self._views(self.ema)
         out["resblocks.0.batch_norm.running_mean"] = self.ema[OFF_RS:OFF_RS + 32]
         out["resblocks.0.batch_norm.running_var"] = self.ema[OFF_RS + 32:OFF_RS + 64]
         return out
@@ -693,10 +694,8 @@ class NetResDeepEngine:
         from .evaluate import evaluate_netresdeep
         if ema:
             self._need_ema()
-            views = self._ema_views()
-            kw["params"] = {name: views[name] for name in LAYOUT}
-            kw.setdefault("bn_stats", (views["resblocks.0.batch_norm.running_mean"],
-                                       views["resblocks.0.batch_norm.running_var"]))
+            kw["params"] = self._views(self.ema)
+            kw.setdefault("bn_stats", (self.ema[OFF_RS:OFF_RS + 32], self.ema[OFF_RS + 32:OFF_RS + 64]))
         kw.setdefault("dtype", self.cfg.dtype)
         kw["stream"] = self.lib.dca_engine_stream(self.h)
         return evaluate_netresdeep(self.model, self.eval_data if data_u8 is None else data_u8,

@@ -13,6 +13,9 @@ the same stdout lines -- while the step itself runs on the MI355X-native path:
   BN + ReLU + residual, fused cross-entropy, HIP SGD; fp8 forward GEMMs with ``fp8``) + ``FlatBucketDDP``.
 * ``engine="torch"``: stock PyTorch ops + ``FlatBucketDDP`` (generic path; CPU / gloo; any model).
 
+``train_loop`` itself is engine-blind: how an epoch's steps run and who holds the optimiser state and the averaged
+weights is behind one of the two step backends of ``backends.py``.
+
 Options beyond the reference (all off by default): max_steps (per epoch), synthetic data, resume, metrics JSON,
 fault injection (``fail_at_step``), process-group timeout, set_epoch reshuffling, bf16/fp32 engine precision,
 momentum / weight decay / a per-step learning-rate schedule (``optimizer_active``; one table drives every engine),
@@ -37,7 +40,7 @@ import torch.nn as nn
 from .data.cifar import load_cifar10
 from .data.loader import DeviceLoader
 from .data.synthetic import synthetic_cifar
-from .utils.checkpoint import CHECKPOINT_NAME, load_checkpoint, save_checkpoint, unwrap
+from .utils.checkpoint import CHECKPOINT_NAME, load_checkpoint, save_checkpoint, save_on_rank0, unwrap
 from .utils.metrics import MetricsLog, epoch_line, should_log, time_line
 
 
@@ -90,72 +93,82 @@ class TrainConfig:
     extra: dict = field(default_factory=dict)
 
 
+_D = TrainConfig()  # the defaults of the flags below: stated once, in the fields above
+
+
 def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argparse.ArgumentParser:
-    ap.add_argument("--epochs", type=int, default=99)
-    ap.add_argument("--max-steps", type=int, default=None, help="cap on steps per epoch")
+    ap.add_argument("--epochs", type=int, default=_D.epochs)
+    ap.add_argument("--max-steps", type=int, default=_D.max_steps, help="cap on steps per epoch")
     ap.add_argument("--batch-size", type=int, default=batch_default)
-    ap.add_argument("--lr", type=float, default=1e-2)
+    ap.add_argument("--lr", type=float, default=_D.lr)
     ap.add_argument("--data-root", default=None)
-    ap.add_argument("--synthetic", type=int, nargs="?", const=50000, default=0,
+    ap.add_argument("--synthetic", type=int, nargs="?", const=50000, default=_D.synthetic,
                     help="train on N synthetic CIFAR-shaped samples (default 50000)")
     ap.add_argument("--synthetic-learnable", action="store_true",
                     help="synthetic data whose label is a function of the image (blended class colour + random-phase "
                          "class stripes under noise, 10%% label noise), so the loss has a learning curve; implies "
                          "--synthetic 50000 unless given")
-    ap.add_argument("--engine", default="auto", choices=["auto", "fused", "ops", "torch"],
+    ap.add_argument("--engine", default=_D.engine, choices=["auto", "fused", "ops", "torch"],
                     help="fused: NetResDeep native engine; ops: the framework's HIP layer kernels (any supported "
                          "model) + FlatBucketDDP; torch: stock PyTorch ops + FlatBucketDDP")
     ap.add_argument("--fp8", action="store_true", help="ops engine: fp8 e4m3 forward GEMMs (1x1 convs, fc)")
-    ap.add_argument("--dtype", default="fp32", choices=["bf16", "fp32"],
+    ap.add_argument("--dtype", default=_D.dtype, choices=["bf16", "fp32"],
                     help="fp32 (default): fp32-accurate, the reference's dtype (the sliced engine computes every "
                          "product as 3 bf16 MFMA products, ~2^-17 relative error; the multi-kernel engine exact fp32 "
                          "MFMA); bf16: bf16 MFMA operands, fp32 accumulation")
     ap.add_argument("--no-checkpoint", action="store_true")
-    ap.add_argument("--checkpoint-path", default=None)
-    ap.add_argument("--resume", default=None)
-    ap.add_argument("--metrics-json", default=None)
-    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--checkpoint-path", default=_D.checkpoint_path)
+    ap.add_argument("--resume", default=_D.resume)
+    ap.add_argument("--metrics-json", default=_D.metrics_json)
+    ap.add_argument("--seed", type=int, default=_D.seed)
     ap.add_argument("--set-epoch", action="store_true", help="reshuffle every epoch (reference never does)")
-    ap.add_argument("--fail-at-step", type=int, default=None, help="fault injection: raise on this global step")
-    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
+    ap.add_argument("--fail-at-step", type=int, default=_D.fail_at_step,
+                    help="fault injection: raise on this global step")
+    ap.add_argument("--backend", default=_D.backend, choices=["nccl", "gloo"])
     ap.add_argument("--world-size", type=int, default=None, help="number of ranks (default: GPU count)")
-    ap.add_argument("--port", type=int, default=None)
-    ap.add_argument("--timeout", type=float, default=None, help="process-group timeout in seconds")
-    ap.add_argument("--model", default="netresdeep", choices=["netresdeep", "resnet50"])
-    ap.add_argument("--bucket-mb", type=float, default=4.0, help="gradient bucket cap (generic DDP path)")
-    ap.add_argument("--profile", default=None, metavar="DIR", help="write torch.profiler traces to DIR")
-    ap.add_argument("--check-sync", type=int, default=0, metavar="N",
+    ap.add_argument("--port", type=int, default=_D.port)
+    ap.add_argument("--timeout", type=float, default=_D.timeout_s, help="process-group timeout in seconds")
+    ap.add_argument("--model", default=_D.model, choices=["netresdeep", "resnet50"])
+    ap.add_argument("--bucket-mb", type=float, default=_D.bucket_mb, help="gradient bucket cap (generic DDP path)")
+    ap.add_argument("--profile", default=_D.profile, metavar="DIR", help="write torch.profiler traces to DIR")
+    ap.add_argument("--check-sync", type=int, default=_D.check_sync, metavar="N",
                     help="assert parameters are identical on all ranks at start and every N epochs")
-    ap.add_argument("--allreduce", default="auto", choices=["auto", "xgmi", "rccl"],
+    ap.add_argument("--allreduce", default=_D.allreduce, choices=["auto", "xgmi", "rccl"],
                     help="fused engine gradient all-reduce: one-shot xGMI peer reads (auto inside a node) or RCCL")
-    ap.add_argument("--eval", type=int, nargs="?", const=0, default=None, metavar="N",
+    ap.add_argument("--eval", type=int, nargs="?", const=0, default=_D.eval, metavar="N",
                     help="after every logged epoch (1, 10, 20, ...) and the last one, print the eval-mode accuracy and "
                          "loss on held-out data: the CIFAR-10 test split (its first N images if N is given), or with "
                          "--synthetic* N (default 10000) fresh synthetic images of the same kind")
     ap.add_argument("--eval-only", action="store_true",
                     help="load --resume, evaluate as --eval does, print the result and exit without training")
-    ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (dampening 0); default 0: plain SGD")
-    ap.add_argument("--weight-decay", type=float, default=0.0,
+    ap.add_argument("--momentum", type=float, default=_D.momentum,
+                    help="SGD momentum (dampening 0); default 0: plain SGD")
+    ap.add_argument("--weight-decay", type=float, default=_D.weight_decay,
                     help="weight decay on every parameter tensor: an L2 term of the gradient (--optimizer sgd, adam) "
                          "or decoupled (adamw)")
-    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adamw"],
+    ap.add_argument("--optimizer", default=_D.optimizer, choices=["sgd", "adam", "adamw"],
                     help="update rule: SGD (default), or torch's Adam / AdamW (amsgrad off) with --adam-beta1, "
                          "--adam-beta2, --adam-eps; --momentum belongs to sgd")
-    ap.add_argument("--adam-beta1", type=float, default=0.9, help="Adam / AdamW: first-moment decay, in [0, 1)")
-    ap.add_argument("--adam-beta2", type=float, default=0.999, help="Adam / AdamW: second-moment decay, in [0, 1)")
-    ap.add_argument("--adam-eps", type=float, default=1e-8, help="Adam / AdamW: the denominator's epsilon, > 0")
-    ap.add_argument("--lr-schedule", default=None, choices=["constant", "step", "cosine"],
+    ap.add_argument("--adam-beta1", type=float, default=_D.adam_beta1,
+                    help="Adam / AdamW: first-moment decay, in [0, 1)")
+    ap.add_argument("--adam-beta2", type=float, default=_D.adam_beta2,
+                    help="Adam / AdamW: second-moment decay, in [0, 1)")
+    ap.add_argument("--adam-eps", type=float, default=_D.adam_eps, help="Adam / AdamW: the denominator's epsilon, > 0")
+    ap.add_argument("--lr-schedule", default=_D.lr_schedule, choices=["constant", "step", "cosine"],
                     help="per-step learning-rate schedule over epochs x steps-per-epoch steps (default: constant --lr)")
-    ap.add_argument("--lr-warmup-steps", type=int, default=0, help="linear warm-up over the first N steps")
-    ap.add_argument("--lr-min", type=float, default=0.0, help="cosine schedule: the final learning rate")
-    ap.add_argument("--lr-step-epochs", type=int, default=None, help="step schedule: decay every N epochs")
-    ap.add_argument("--lr-gamma", type=float, default=0.1, help="step schedule: decay factor")
+    ap.add_argument("--lr-warmup-steps", type=int, default=_D.lr_warmup_steps,
+                    help="linear warm-up over the first N steps")
+    ap.add_argument("--lr-min", type=float, default=_D.lr_min, help="cosine schedule: the final learning rate")
+    ap.add_argument("--lr-step-epochs", type=int, default=_D.lr_step_epochs,
+                    help="step schedule: decay every N epochs")
+    ap.add_argument("--lr-gamma", type=float, default=_D.lr_gamma, help="step schedule: decay factor")
     ap.add_argument("--augment", action="store_true",
                     help="training images only: every epoch a fresh random crop (zero padding --augment-pad) and "
                          "horizontal flip of each image, as one on-device pass over the uint8 dataset")
-    ap.add_argument("--augment-pad", type=int, default=4, metavar="N", help="crop padding in pixels, 0..8 (default 4)")
+    ap.add_argument("--augment-pad", type=int, default=_D.augment_pad, metavar="N",
+                    help="crop padding in pixels, 0..8 (default 4)")
     ap.add_argument("--augment-no-flip", action="store_true", help="--augment without the horizontal flip")
-    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+    ap.add_argument("--ema-decay", type=float, default=_D.ema_decay, metavar="D",
                     help="keep an exponential moving average of the parameters and BatchNorm running statistics with "
                          "decay D in [0, 1), updated after every optimiser step; --eval also reports it and every "
                          "checkpoint gets a <checkpoint>.ema.pt beside it (default: off)")
@@ -164,53 +177,43 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     return ap
 
 
+# flag (its argparse dest) -> TrainConfig field, where the two differ; every other flag sets the field of its own name
+_RENAMED = {"data_root": "data_path", "timeout": "timeout_s"}
+_NEGATED = {"no_checkpoint": "checkpoint", "augment_no_flip": "augment_flip"}
+
+
 def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConfig:
-    learnable = bool(getattr(a, "synthetic_learnable", False))
-    eval_only = bool(getattr(a, "eval_only", False))
-    if eval_only and not a.resume:
+    """The run's ``TrainConfig``; a field whose flag the namespace lacks keeps its default.  Values no run can take
+    exit here."""
+    fields = TrainConfig.__dataclass_fields__
+    kw = {}
+    for dest, value in vars(a).items():
+        if dest in _NEGATED:
+            kw[_NEGATED[dest]] = not value
+        elif _RENAMED.get(dest, dest) in fields:
+            kw[_RENAMED.get(dest, dest)] = value
+    kw["data_path"] = kw.get("data_path") or data_path_default
+    cfg = TrainConfig(**kw)
+    if cfg.synthetic_learnable and not cfg.synthetic:
+        cfg.synthetic = 50000
+    if cfg.eval_only and not cfg.resume:
         raise SystemExit("--eval-only requires --resume")
-    n_eval = getattr(a, "eval", None)
-    if n_eval is not None and n_eval < 0:
+    if cfg.eval is not None and cfg.eval < 0:
         raise SystemExit("--eval N: N must not be negative")
-    return TrainConfig(eval=0 if eval_only and n_eval is None else n_eval, eval_only=eval_only,
-                       epochs=a.epochs, lr=a.lr, batch_size=a.batch_size, data_path=a.data_root or data_path_default,
-                       synthetic=a.synthetic or (50000 if learnable else 0), synthetic_learnable=learnable,
-                       engine=a.engine, dtype=a.dtype, max_steps=a.max_steps,
-                       checkpoint=not a.no_checkpoint, checkpoint_path=a.checkpoint_path, resume=a.resume,
-                       metrics_json=a.metrics_json, seed=a.seed, set_epoch=a.set_epoch, fail_at_step=a.fail_at_step,
-                       backend=a.backend, port=a.port, timeout_s=a.timeout, model=a.model, bucket_mb=a.bucket_mb,
-                       profile=a.profile, check_sync=a.check_sync, allreduce=a.allreduce, fp8=a.fp8,
-                       momentum=getattr(a, "momentum", 0.0), weight_decay=getattr(a, "weight_decay", 0.0),
-                       lr_schedule=getattr(a, "lr_schedule", None), lr_warmup_steps=getattr(a, "lr_warmup_steps", 0),
-                       lr_min=getattr(a, "lr_min", 0.0), lr_step_epochs=getattr(a, "lr_step_epochs", None),
-                       lr_gamma=getattr(a, "lr_gamma", 0.1), augment=bool(getattr(a, "augment", False)),
-                       augment_pad=getattr(a, "augment_pad", 4),
-                       augment_flip=not getattr(a, "augment_no_flip", False),
-                       ema_decay=_ema_decay_arg(getattr(a, "ema_decay", None)),
-                       ema_warmup=bool(getattr(a, "ema_warmup", False)), **_optimizer_args(a))
-
-
-def _optimizer_args(a: argparse.Namespace) -> dict:
-    """The ``--optimizer`` / ``--adam-*`` fields of ``TrainConfig``; values no optimiser takes exit here."""
-    kind = getattr(a, "optimizer", "sgd")
-    out = dict(optimizer=kind, adam_beta1=getattr(a, "adam_beta1", 0.9), adam_beta2=getattr(a, "adam_beta2", 0.999),
-               adam_eps=getattr(a, "adam_eps", 1e-8))
-    if kind != "sgd":
-        if getattr(a, "momentum", 0.0):
-            raise SystemExit(f"--momentum belongs to --optimizer sgd; --optimizer {kind} takes --adam-beta1 / "
+    if cfg.eval_only and cfg.eval is None:
+        cfg.eval = 0
+    if cfg.ema_decay is not None and not 0.0 <= cfg.ema_decay < 1.0:
+        raise SystemExit("--ema-decay must lie in [0, 1)")
+    if cfg.optimizer != "sgd":  # values no Adam takes
+        if cfg.momentum:
+            raise SystemExit(f"--momentum belongs to --optimizer sgd; --optimizer {cfg.optimizer} takes --adam-beta1 / "
                              f"--adam-beta2")
         from .utils.schedule import check_adam
         try:
-            check_adam(out["adam_beta1"], out["adam_beta2"], out["adam_eps"], getattr(a, "weight_decay", 0.0))
+            check_adam(cfg.adam_beta1, cfg.adam_beta2, cfg.adam_eps, cfg.weight_decay)
         except ValueError as ex:
-            raise SystemExit(f"--optimizer {kind}: {ex}")
-    return out
-
-
-def _ema_decay_arg(decay):
-    if decay is not None and not 0.0 <= decay < 1.0:
-        raise SystemExit("--ema-decay must lie in [0, 1)")
-    return decay
+            raise SystemExit(f"--optimizer {cfg.optimizer}: {ex}")
+    return cfg
 
 
 def optimizer_active(cfg: TrainConfig) -> bool:
@@ -289,76 +292,40 @@ def make_adam(model, cfg: TrainConfig):
     return cls(model.parameters(), lr=cfg.lr, betas=betas, eps=cfg.adam_eps, weight_decay=cfg.weight_decay)
 
 
-def _flat_views(model, flat, buf) -> dict:
-    """{parameter name: view of `buf`}, `buf` laid out like the flat parameter buffer `flat`."""
-    out = {}
-    for name, p in unwrap(model).named_parameters():
-        off = (p.data_ptr() - flat.data_ptr()) // flat.element_size()
-        out[name] = buf[off:off + p.numel()].view(p.shape)
-    return out
+def make_optimizer(model, cfg: TrainConfig, table):
+    """The generic engines' optimiser: ``FlatSGD`` / ``FlatAdam`` over a ``FlatBucketDDP``, torch's own for a plain
+    module.  No optimiser option on (`table` None): the reference's SGD(lr), built with nothing else."""
+    from .parallel import flat_ddp  # (the classes are looked up when called: tests spy on them)
+    flat = isinstance(model, flat_ddp.FlatBucketDDP)
+    if table is None:
+        return flat_ddp.FlatSGD(model, cfg.lr) if flat else torch.optim.SGD(model.parameters(), lr=cfg.lr)
+    if cfg.optimizer != "sgd":
+        return make_adam(model, cfg)
+    args = dict(momentum=cfg.momentum, weight_decay=cfg.weight_decay)
+    return flat_ddp.FlatSGD(model, cfg.lr, **args) if flat else torch.optim.SGD(model.parameters(), lr=cfg.lr, **args)
 
 
-def _state_buffers(model, optimizer, key: str) -> dict:
-    """{parameter name: the optimiser's per-parameter state tensor `key`} of a torch optimiser (tensors absent before
-    the first step)."""
-    return {name: optimizer.state[p][key] for name, p in unwrap(model).named_parameters()
-            if optimizer.state.get(p, {}).get(key) is not None}
+_STATE_TENSORS = ("momentum_buffer", "exp_avg", "exp_avg_sq")  # the sidecar's {parameter name: tensor} entries
 
 
-def _momentum_buffers(model, optimizer) -> dict:
-    """{parameter name: momentum buffer} of the generic engines' optimiser (tensors absent before the first step)."""
-    from .parallel.flat_ddp import FlatSGD
-    if isinstance(optimizer, FlatSGD):
-        if optimizer._buf is None:
-            return {}
-        return _flat_views(model, optimizer.ddp.flat, optimizer._buf)
-    return _state_buffers(model, optimizer, "momentum_buffer")
-
-
-def _adam_moments(model, optimizer) -> tuple:
-    """({parameter name: exp_avg}, {parameter name: exp_avg_sq}) of the generic engines' Adam optimiser."""
-    from .parallel.flat_ddp import FlatAdam
-    if isinstance(optimizer, FlatAdam):
-        flat = optimizer.ddp.flat
-        return _flat_views(model, flat, optimizer.exp_avg), _flat_views(model, flat, optimizer.exp_avg_sq)
-    return _state_buffers(model, optimizer, "exp_avg"), _state_buffers(model, optimizer, "exp_avg_sq")
-
-
-def save_optimizer_state(model, optimizer, path: str, rank: int, step: int, kind: str = "sgd") -> None:
+def save_optimizer_state(backend, path: str, rank: int, step: int) -> None:
     """Rank 0 writes ``<checkpoint>.optim.pt`` (atomically): ``{"step", "momentum_buffer": {name: CPU tensor}}``, or
-    with `kind` ``adam`` / ``adamw`` ``{"step", "kind", "exp_avg": {...}, "exp_avg_sq": {...}}``."""
-    from .parallel.ddp import FusedDDPTrainer
+    with ``--optimizer adam`` / ``adamw`` ``{"step", "kind", "exp_avg": {...}, "exp_avg_sq": {...}}``; the fused
+    engine adds ``"engine"``, its step kernels' carried state."""
     if rank != 0:
         return
-
-    def cpu(bufs):
-        return {k: v.detach().to("cpu", copy=True) for k, v in bufs.items()}
-    extra = {}
-    if isinstance(model, FusedDDPTrainer):
-        st = model.engine.optimizer_state()
-        extra["engine"] = model.engine.step_state()  # the step kernels' carried BN shifts (bitwise resume)
-    elif kind != "sgd":
-        st = dict(zip(("exp_avg", "exp_avg_sq"), _adam_moments(model, optimizer)))
-    else:
-        st = {"momentum_buffer": _momentum_buffers(model, optimizer)}
-    if kind != "sgd":
-        state = {"step": int(step), "kind": kind, "exp_avg": cpu(st["exp_avg"]), "exp_avg_sq": cpu(st["exp_avg_sq"]),
-                 **extra}
-    else:
-        state = {"step": int(step), "momentum_buffer": cpu(st["momentum_buffer"]), **extra}
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = f"{optim_path(path)}.tmp.{os.getpid()}"
-    torch.save(state, tmp)
-    os.replace(tmp, optim_path(path))
+    state = {"step": int(step)}
+    for key, value in backend.optimizer_state().items():
+        state[key] = {k: v.detach().to("cpu", copy=True) for k, v in value.items()} if key in _STATE_TENSORS else value
+    save_on_rank0(state, optim_path(path))
 
 
-def load_optimizer_state(model, optimizer, path: str, step: int, kind: str = "sgd") -> bool:
+def load_optimizer_state(backend, path: str, step: int, kind: str = "sgd") -> bool:
     """Restore ``<checkpoint>.optim.pt`` if present (momentum buffers or Adam moments; the step counter <- `step`).
     A sidecar written by another optimiser kind than `kind` ends the run (one without ``"kind"`` is SGD's)."""
-    from .parallel.ddp import FusedDDPTrainer
-    from .parallel.flat_ddp import FlatAdam, FlatSGD
     from .runtime.engine import optimizer_state_kind
     if not os.path.exists(optim_path(path)):
+        backend.load_optimizer_state(None, step)
         return False
     state = torch.load(optim_path(path), map_location="cpu", weights_only=True)
     theirs = optimizer_state_kind(state)
@@ -366,43 +333,7 @@ def load_optimizer_state(model, optimizer, path: str, step: int, kind: str = "sg
         raise SystemExit(f"--resume: {optim_path(path)} holds the state of --optimizer {theirs}, this run uses "
                          f"--optimizer {kind}; resume with --optimizer {theirs}, or remove the file to restart the "
                          f"optimiser state")
-    if isinstance(model, FusedDDPTrainer):
-        model.engine.load_optimizer_state({**{k: v for k, v in state.items() if k != "engine"}, "step": int(step)})
-        if "engine" in state:
-            model.engine.load_step_state(state["engine"])
-        return True
-    named = dict(unwrap(model).named_parameters())
-    if kind != "sgd":
-        m, v = state["exp_avg"], state["exp_avg_sq"]
-        with torch.no_grad():
-            if isinstance(optimizer, FlatAdam):
-                flat = optimizer.ddp.flat
-                for bufs, dst in ((m, optimizer.exp_avg), (v, optimizer.exp_avg_sq)):
-                    if bufs:
-                        for name, view in _flat_views(model, flat, dst).items():
-                            view.copy_(bufs[name])
-                optimizer.set_steps_taken(int(step))
-            elif m:
-                for name, p in named.items():
-                    optimizer.state[p] = {"step": torch.tensor(float(step)),
-                                          "exp_avg": m[name].to(p.device, p.dtype).clone(),
-                                          "exp_avg_sq": v[name].to(p.device, p.dtype).clone()}
-        return True
-    bufs = state["momentum_buffer"]
-    if not bufs:
-        return True
-    with torch.no_grad():
-        if isinstance(optimizer, FlatSGD):
-            flat = optimizer.ddp.flat
-            optimizer._buf = torch.zeros_like(flat)
-            if flat.is_cuda:  # the HIP kernel's "buffer not initialised yet" flag: it is now
-                optimizer._first = torch.zeros(1, dtype=torch.int32, device=flat.device)
-            for name, p in named.items():
-                off = (p.data_ptr() - flat.data_ptr()) // flat.element_size()
-                optimizer._buf[off:off + p.numel()].copy_(bufs[name].reshape(-1))
-        else:
-            for name, p in named.items():
-                optimizer.state[p]["momentum_buffer"] = bufs[name].to(p.device, p.dtype).clone()
+    backend.load_optimizer_state(state, step)
     return True
 
 
@@ -437,27 +368,8 @@ def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False, ema=No
     eval mode.  `ema`: evaluate the averaged model instead -- ``True`` for a ``FusedDDPTrainer`` (its engine's
     average, read in place), the ``ModelEma`` of any other model (swapped into the module for the call); every rank
     evaluates with rank 0's averaged running statistics, as with the live ones."""
-    from .parallel.ddp import FusedDDPTrainer
-    from .parallel.flat_ddp import FlatBucketDDP
-    from .runtime.evaluate import evaluate_distributed, evaluate_module
-    if isinstance(model, FusedDDPTrainer):
-        if ema:
-            from .runtime.engine import OFF_RS
-            avg = model.engine.ema
-            return evaluate_distributed(model.module, data, labels, bn_stats_src=(avg[OFF_RS:OFF_RS + 32],
-                                                                                   avg[OFF_RS + 32:OFF_RS + 64]),
-                                        evaluate=lambda d, l, i, **kw: model.engine.evaluate(d, l, i, ema=True, **kw))
-        return evaluate_distributed(model.module, data, labels, evaluate=model.engine.evaluate)
-    if ema is not None:
-        with ema.swapped_in():
-            return run_eval(model, data, labels, cfg, kernel=kernel)
-    if kernel:
-        return evaluate_distributed(model, data, labels, dtype=cfg.dtype)
-    fwd = model.module if isinstance(model, FlatBucketDDP) else model  # an OpsModel stays wrapped: its HIP kernels
-    if isinstance(model, FlatBucketDDP) and model.broadcast_buffers:
-        model._broadcast_buffers_now()  # rank 0's buffers, as the wrapper's next forward would install them anyway
-    return evaluate_distributed(unwrap(model), data, labels, sync_bn_stats=False,
-                                evaluate=lambda d, l, i: evaluate_module(fwd, d, l, i))
+    from .backends import evaluate_model
+    return evaluate_model(model, data, labels, cfg.dtype, kernel=kernel, ema=ema)
 
 
 def eval_only(cfg: TrainConfig, device: torch.device, rank: int = 0):
@@ -500,87 +412,45 @@ def resolve_engine(cfg: TrainConfig, device: torch.device, model: nn.Module) -> 
         return cfg.engine
     if device.type != "cuda":
         return "torch"
-    return "fused" if _is_netresdeep(model) and cfg.batch_size <= FUSED_BATCH_MAX else "ops"
+    return "fused" if is_netresdeep(model) and cfg.batch_size <= FUSED_BATCH_MAX else "ops"
 
 
-def _is_netresdeep(model: nn.Module) -> bool:
+def is_netresdeep(model: nn.Module) -> bool:
     return getattr(model, "n_chans1", None) == 32 and getattr(model, "n_blocks", None) == 10
-
-
-class _Fault(RuntimeError):
-    pass
 
 
 def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[TrainConfig] = None,
                optimizer=None) -> dict:
     """Reference ``main.py:26-49`` / ``main_no_ddp.py:36-59``.  `model` is a ``FusedDDPTrainer`` (engine path),
     a ``FlatBucketDDP`` or a plain module (torch path).  Returns a summary dict."""
-    from .parallel.ddp import FusedDDPTrainer
+    from contextlib import ExitStack
+    from .backends import step_backend
+    from .parallel.dist import assert_params_in_sync
+    from .utils.ema import ema_decay_at, load_ema_state, save_ema_state
     cfg = cfg or TrainConfig()
     mlog = MetricsLog(cfg.metrics_json, rank)
     ckpt = cfg.checkpoint_path or os.path.join(cfg.data_path, CHECKPOINT_NAME)
-    fused = isinstance(model, FusedDDPTrainer)
     n_batches = len(train_loader)
     steps_per_epoch = steps_per_epoch_of(cfg, n_batches)
     table = lr_table_for(cfg, n_batches)  # None: no optimiser option on, everything below as in the reference
     start_epoch = int(cfg.extra.get("start_epoch", 1))
     global_step = int(cfg.extra.get("start_step", 0))
+    opt_step = int(cfg.extra.get("opt_step", global_step))
     history = []
-    from .ops.models import OpsModel
-    on_ops = isinstance(getattr(model, "module", None), OpsModel)
-    if not fused:
-        loss_fn = nn.CrossEntropyLoss()
-        if on_ops:
-            from .ops.functional import cross_entropy as loss_fn
-        if optimizer is None:
-            from .parallel.flat_ddp import FlatBucketDDP, FlatSGD
-            if table is None:
-                optimizer = FlatSGD(model, cfg.lr) if isinstance(model, FlatBucketDDP) else \
-                    torch.optim.SGD(model.parameters(), lr=cfg.lr)
-            elif cfg.optimizer != "sgd":
-                optimizer = make_adam(model, cfg)
-            else:
-                optimizer = FlatSGD(model, cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay) \
-                    if isinstance(model, FlatBucketDDP) else \
-                    torch.optim.SGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                                    weight_decay=cfg.weight_decay)
+    backend = step_backend(model, cfg, rank, table, optimizer, lambda m: make_optimizer(m, cfg, table))
     if table is not None:
-        from .utils.schedule import lr_at
-        if fused and model.engine.cfg.optimizer is None:
-            raise ValueError("optimiser options are on but the fused trainer was built without optimizer= "
-                             "(train.engine_optimizer)")
-        opt_step = int(cfg.extra.get("opt_step", global_step))
         if cfg.resume:  # momentum buffers of the run being resumed (absent file: they start at zero)
-            load_optimizer_state(model, optimizer, cfg.resume, opt_step, cfg.optimizer)
-        if fused and opt_step != model.engine.optimizer_step():  # the schedule position (no sidecar to restore)
-            model.engine.load_optimizer_state({**model.engine.optimizer_state(), "step": opt_step})
-    ema = None  # the generic engines' averager; the fused engine keeps its average in the optimiser pass
-    if cfg.ema_decay is not None:
-        from .utils.ema import ModelEma, ema_decay_at, load_ema_state, save_ema_state
-        if fused and model.engine.ema is None:
-            raise ValueError("--ema-decay is on but the fused trainer was built without it (train.engine_optimizer)")
-        if not fused:
-            ema = ModelEma(model, cfg.ema_decay, cfg.ema_warmup)
-        if cfg.resume:  # the average of the run being resumed (absent file: it restarts from the loaded parameters)
-            avg = load_ema_state(cfg.resume)
-            if avg is None:
-                print(f"warning: no {cfg.resume}.ema.pt: the EMA restarts from the loaded parameters", file=sys.stderr)
-            elif fused:
-                model.engine.load_ema_state_dict(avg)
-            else:
-                ema.load_state_dict(avg)
-    last_lr = cfg.lr
-    from contextlib import ExitStack
-    from .utils.trace import trace_range as record_function  # torch.profiler + roctx ranges
-    from .parallel.dist import assert_params_in_sync
-    autocast = (not fused and not on_ops and cfg.dtype == "bf16" and train_loader.device.type == "cuda"
-                and not _is_netresdeep(unwrap(model)))  # generic models train in bf16; NetResDeep torch path = fp32
+            load_optimizer_state(backend, cfg.resume, opt_step, cfg.optimizer)
+        else:
+            backend.load_optimizer_state(None, opt_step)  # only the schedule position
+    if cfg.ema_decay is not None and cfg.resume:
+        avg = load_ema_state(cfg.resume)  # the average of the run being resumed
+        if avg is None:  # absent file: it restarts from the loaded parameters
+            print(f"warning: no {cfg.resume}.ema.pt: the EMA restarts from the loaded parameters", file=sys.stderr)
+        else:
+            backend.load_ema_state(avg)
     if cfg.check_sync:
         assert_params_in_sync(unwrap(model))
-    if cfg.metrics_json and hasattr(model, "timing"):
-        model.timing = True  # FlatBucketDDP: record the comm-stream span per step
-    if cfg.metrics_json and fused:
-        model.engine.comm_time(reset=True)
     eval_set = load_eval_dataset(cfg) if cfg.eval is not None else None
     if eval_set is not None:
         eval_set = (eval_set[0].to(train_loader.device), eval_set[1].to(train_loader.device))
@@ -590,85 +460,47 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
     for epoch in range(start_epoch, cfg.epochs + 1):
         train_loader.set_epoch(epoch)
         t0 = time.perf_counter()
-        if fused:
-            bs = train_loader.batch_size
-            idx = train_loader.indices()[:steps_per_epoch * bs]
-            if getattr(train_loader, "augment", None) is not None:
-                # this epoch's crops and flips of the rows the epoch reads, on the engine's stream: after the last
-                # epoch's steps and before set_indices, which stages the first batch from `data`
-                train_loader.augment_epoch(idx, stream=model.engine.lib.dca_engine_stream(model.engine.h))
-            if cfg.fail_at_step is not None and global_step < cfg.fail_at_step <= global_step + steps_per_epoch:
-                done = cfg.fail_at_step - global_step - 1  # steps before the failing one still run, as on the
-                if done:                                   # generic path (the failure is raised AT that step)
-                    model.engine.run_epoch(idx[:done * bs], bs)
-                raise _Fault(f"injected failure at step {cfg.fail_at_step} (rank {rank})")
-            with record_function(f"epoch{epoch}:engine"):
-                loss_sum, nsteps = model.engine.run_epoch(idx, bs)
-        else:
-            loss_sum, nsteps = 0.0, 0
-            for imgs, labels in train_loader:
-                if nsteps >= steps_per_epoch:
-                    break
-                if cfg.fail_at_step is not None and global_step + nsteps + 1 == cfg.fail_at_step:
-                    raise _Fault(f"injected failure at step {cfg.fail_at_step} (rank {rank})")
-                if table is not None:  # this step's learning rate (the fused engine reads the same table on the GPU)
-                    last_lr = lr_at(table, opt_step + nsteps)
-                    for group in optimizer.param_groups:
-                        group["lr"] = last_lr
-                with record_function("forward"), torch.autocast("cuda", torch.bfloat16, enabled=autocast):
-                    outputs = model(imgs)
-                    loss = loss_fn(outputs.float(), labels)
-                optimizer.zero_grad()
-                with record_function("backward+allreduce"):
-                    loss.backward(_seed_grad(loss))
-                with record_function("optimizer"):
-                    optimizer.step()
-                    if ema is not None:
-                        ema.update(opt_step + nsteps)
-                loss_sum += loss.item()
-                nsteps += 1
+        fail_after = None  # --fail-at-step inside this epoch: the steps before the failing one still run
+        if cfg.fail_at_step is not None and global_step < cfg.fail_at_step <= global_step + steps_per_epoch:
+            fail_after = cfg.fail_at_step - global_step - 1
+        loss_sum, nsteps, last_lr = backend.run_epoch(train_loader, steps_per_epoch, opt_step, fail_after)
         global_step += nsteps
         if table is not None:
             opt_step += nsteps
-            if nsteps:
-                last_lr = lr_at(table, opt_step - 1)
         dt = time.perf_counter() - t0
-        if hasattr(model, "check_comm"):  # a peer timeout of the xGMI all-reduce must not go unnoticed
-            model.check_comm()            # (rank-divergent gradients): raise before anything is saved
+        backend.check_comm()  # a peer timeout (rank-divergent gradients): raise before anything is saved
         mean = loss_sum / n_batches  # reference divides by len(train_loader) (main.py:44)
         history.append(mean)
-        comm_us, comm_n = _comm_time(model) if cfg.metrics_json else (0.0, 0)
-        eng = getattr(model, "engine", None)
-        ev = run_eval(model, *eval_set, cfg) if eval_set is not None and (should_log(epoch) or epoch == cfg.epochs) \
-            else None
-        ev_rec = dict(eval_accuracy=ev.accuracy, eval_loss=ev.mean_loss, eval_images=ev.count) if ev else {}
-        ema_ev = run_eval(model, *eval_set, cfg, ema=True if fused else ema) \
-            if ev is not None and cfg.ema_decay is not None else None
-        if ema_ev is not None:
-            ev_rec.update(ema_eval_accuracy=ema_ev.accuracy, ema_eval_loss=ema_ev.mean_loss)
+        comm_us, comm_n = backend.comm_time() if cfg.metrics_json else (0.0, 0)
+        ev = ema_ev = None
+        ev_rec = {}
+        if eval_set is not None and (should_log(epoch) or epoch == cfg.epochs):
+            ev = backend.evaluate(*eval_set)
+            ev_rec = dict(eval_accuracy=ev.accuracy, eval_loss=ev.mean_loss, eval_images=ev.count)
+            if cfg.ema_decay is not None:
+                ema_ev = backend.evaluate(*eval_set, ema=True)
+                ev_rec.update(ema_eval_accuracy=ema_ev.accuracy, ema_eval_loss=ema_ev.mean_loss)
         mlog.write(epoch=epoch, loss=mean, steps=nsteps, seconds=dt, step_ms=1e3 * dt / max(nsteps, 1),
                    images_per_sec=nsteps * train_loader.batch_size / max(dt, 1e-9),
                    # exposed wait of the reduction kernel's gradient-segment exchanges, summed per step (xGMI)
                    allreduce_us_per_step=(comm_us / comm_n) if comm_n else None,
-                   engine=getattr(eng, "kind_name", cfg.engine if not fused else None),
+                   engine=backend.engine_name,
                    lr=last_lr,  # the learning rate of the epoch's last step
                    augment=_augment_record(train_loader),
                    # the decay of the epoch's last EMA update
                    ema_decay=ema_decay_at(opt_step - 1, cfg.ema_decay, cfg.ema_warmup)
                    if cfg.ema_decay is not None and opt_step > 0 else None,
-                   dtype=cfg.dtype, fp32_mode=("3xbf16" if getattr(eng, "kind_name", "") == "sliced" else
-                                               "fp32-mfma") if cfg.dtype == "fp32" and fused else None,
-                   **ev_rec)
+                   dtype=cfg.dtype, fp32_mode=backend.fp32_mode, **ev_rec)
         if should_log(epoch):
             print(epoch_line(epoch, mean), flush=True)
             if cfg.checkpoint:
                 meta = {"epoch": epoch, "step": global_step}
                 if table is not None:  # optimiser sidecar: momentum buffers + the schedule position
                     meta["opt_step"] = opt_step
-                    save_optimizer_state(model, optimizer, ckpt, rank, opt_step, cfg.optimizer)
+                    save_optimizer_state(backend, ckpt, rank, opt_step)
                 save_checkpoint(model, ckpt, rank, meta=meta)
                 if cfg.ema_decay is not None and rank == 0:  # the averaged model, loadable like the checkpoint itself
-                    save_ema_state(model.engine.ema_state_dict() if fused else ema.state_dict(), ckpt, rank)
+                    save_ema_state(backend.ema_state(), ckpt, rank)
         if ev is not None and rank == 0:
             print(eval_line(epoch, ev.accuracy, ev.mean_loss), flush=True)
             if ema_ev is not None:
@@ -699,28 +531,6 @@ def _num_batches_tracked(module) -> Optional[int]:
     return None
 
 
-_SEEDS = {}
-
-
-def _seed_grad(loss: torch.Tensor) -> torch.Tensor:
-    """The scalar loss's seed gradient (1.0), allocated once per device and dtype: ``loss.backward()`` would launch
-    a fill kernel for it every step."""
-    key = (loss.device, loss.dtype)
-    if key not in _SEEDS:
-        _SEEDS[key] = torch.ones((), device=loss.device, dtype=loss.dtype)
-    return _SEEDS[key]
-
-
-def _comm_time(model) -> tuple:
-    """(microseconds, steps) spent in the gradient all-reduce since the last call (per-rank metric)."""
-    from .parallel.ddp import FusedDDPTrainer
-    if isinstance(model, FusedDDPTrainer):
-        return model.engine.comm_time(reset=True)
-    if hasattr(model, "comm_time"):
-        return model.comm_time(reset=True)
-    return 0.0, 0
-
-
 def _profiler(out_dir: str, device: torch.device):
     """torch.profiler over the training loop (CPU ops + HIP kernels through roctracer on ROCm)."""
     from torch.profiler import ProfilerActivity, profile
@@ -741,8 +551,6 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
     """The model wrapped for data parallelism on `device`: NetResDeep on the fused engine, or any model on
     FlatBucketDDP (``--model resnet50`` trains a 10-class ResNet-50 on the CIFAR tensors, channels-last, bf16)."""
     from .models.netresdeep import NetResDeep
-    from .parallel.ddp import FusedDDPTrainer
-    from .parallel.flat_ddp import FlatBucketDDP
     if cfg.model == "resnet50":
         from .models.resnet50 import resnet50
         torch.manual_seed(cfg.seed)
@@ -761,8 +569,19 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
             cfg.extra["start_step"] = int(meta.get("step", 0))
             if "opt_step" in meta:
                 cfg.extra["opt_step"] = int(meta["opt_step"])
+    return wrap_model(cfg, model, loader, device)
+
+
+def wrap_model(cfg: TrainConfig, model: nn.Module, loader: DeviceLoader, device: torch.device,
+               full_device: bool = False):
+    """`model` as ``train_loop`` takes it, by ``resolve_engine``: a ``FusedDDPTrainer``, a ``FlatBucketDDP`` around an
+    ``OpsModel``, or for stock torch ops a ``FlatBucketDDP`` around the module.  `full_device`: one process on a
+    dedicated device (``main_no_ddp.py``) -- the fused engine may take every CU, and stock torch ops need no wrapper:
+    the plain module."""
+    from .parallel.ddp import FusedDDPTrainer
+    from .parallel.flat_ddp import FlatBucketDDP
     kind = resolve_engine(cfg, device, model)
-    if kind == "ops":
+    if kind == "ops":  # the ops-layer HIP kernels (flat parameters, packed weights, HIP SGD)
         from .ops.models import OpsModel
         if device.type != "cuda":
             raise ValueError("--engine ops runs the HIP kernels: it needs a GPU")
@@ -773,6 +592,6 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
         # dataset, is then what engine.evaluate() reads by default
         return FusedDDPTrainer(model, loader.data, loader.labels, batch_max=loader.batch_size, lr=cfg.lr,
                                dtype=cfg.dtype, max_indices=max(n_idx, loader.batch_size), comm=cfg.allreduce,
-                               optimizer=engine_optimizer(cfg, len(loader)), **eval_source(loader))
-    return FlatBucketDDP(model, bucket_cap_mb=cfg.bucket_mb)
-
+                               full_device=full_device, optimizer=engine_optimizer(cfg, len(loader)),
+                               **eval_source(loader))
+    return model if full_device else FlatBucketDDP(model, bucket_cap_mb=cfg.bucket_mb)

@@ -32,9 +32,9 @@ def unwrap(model: nn.Module) -> nn.Module:
     return model
 
 
-def export_state_dict(model: nn.Module) -> dict:
-    """The reference-format state_dict: un-prefixed keys, tensors on the CPU (aliasing preserved)."""
-    sd = unwrap(model).state_dict()
+def cpu_state_dict(sd: dict) -> dict:
+    """A CPU copy of the state_dict `sd` (same dict type and ``_metadata``); keys that share a tensor keep sharing one
+    in the copy, so the file has as many storages as the model has tensors."""
     cache = {}
     out = type(sd)()
     for k, v in sd.items():
@@ -47,21 +47,35 @@ def export_state_dict(model: nn.Module) -> dict:
     return out
 
 
-def save_checkpoint(model: nn.Module, path: str, rank: int = 0, meta: Optional[dict] = None) -> Optional[str]:
-    """Rank 0 writes `path` atomically; other ranks return None without touching the file."""
+def export_state_dict(model: nn.Module) -> dict:
+    """The reference-format state_dict: un-prefixed keys, tensors on the CPU (aliasing preserved)."""
+    return cpu_state_dict(unwrap(model).state_dict())
+
+
+def save_on_rank0(obj, path: str, rank: int = 0, dump=torch.save) -> Optional[str]:
+    """Rank 0 writes `obj` to `path` with ``dump(obj, file name)``, atomically (tmp file + ``os.replace``; the
+    directory is created); other ranks return None without touching the file."""
     if rank != 0:
         return None
-    d = os.path.dirname(os.path.abspath(path))
-    os.makedirs(d, exist_ok=True)
-    sd = export_state_dict(model)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = f"{path}.tmp.{os.getpid()}"
-    torch.save(sd, tmp)
+    dump(obj, tmp)
     os.replace(tmp, path)
+    return path
+
+
+def _dump_json(obj, name: str) -> None:
+    with open(name, "w") as f:
+        json.dump(obj, f)
+
+
+def save_checkpoint(model: nn.Module, path: str, rank: int = 0, meta: Optional[dict] = None) -> Optional[str]:
+    """Rank 0 writes `path` (and `meta` as ``<path>.meta.json``); other ranks return None without touching a file."""
+    if rank != 0:
+        return None
+    save_on_rank0(export_state_dict(model), path)
     if meta is not None:
-        mtmp = f"{path}.meta.json.tmp.{os.getpid()}"
-        with open(mtmp, "w") as f:
-            json.dump(meta, f)
-        os.replace(mtmp, f"{path}.meta.json")
+        save_on_rank0(meta, f"{path}.meta.json", dump=_dump_json)
     return path
 
 

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .checkpoint import unwrap
+from .checkpoint import cpu_state_dict, save_on_rank0, unwrap
 
 WARMUP_NUM, WARMUP_DEN = 1.0, 10.0  # warm-up decay of update k: (1 + k) / (10 + k)
 
@@ -64,20 +64,8 @@ def save_ema_state(state: dict, checkpoint_path: str, rank: int = 0) -> Optional
     tensors, the model's keys), so it loads strictly into the model and ``--eval-only --resume`` evaluates it."""
     if rank != 0:
         return None
-    path = ema_path(checkpoint_path)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    out, cache = type(state)(), {}
-    for k, v in state.items():  # (keys that share a tensor keep sharing it in the file, as in the checkpoint)
-        key = (v.data_ptr(), tuple(v.shape), v.dtype)
-        if key not in cache:
-            cache[key] = v.detach().to("cpu", copy=True)
-        out[k] = cache[key]
-    if hasattr(state, "_metadata"):
-        out._metadata = state._metadata
-    tmp = f"{path}.tmp.{os.getpid()}"
-    torch.save(out, tmp)
-    os.replace(tmp, path)
-    return path
+    # (keys that share a tensor keep sharing it in the file, as in the checkpoint)
+    return save_on_rank0(cpu_state_dict(state), ema_path(checkpoint_path))
 
 
 def load_ema_state(checkpoint_path: str) -> Optional[dict]:
@@ -106,11 +94,7 @@ class ModelEma:
             self._pavg_flat = self._flat.detach().clone() if self._flat is not None else None
             if self._pavg_flat is not None:
                 # views of the averaged flat buffer where the live parameters are views of the live one
-                esz = self._flat.element_size()
-                self.params = {}
-                for n, p in self.net.named_parameters():
-                    off = (p.data_ptr() - self._flat.data_ptr()) // esz
-                    self.params[n] = self._pavg_flat[off:off + p.numel()].view(p.shape)
+                self.params = model.named_views(self._pavg_flat)
             else:
                 self.params = {n: p.detach().clone() for n, p in self.net.named_parameters()}
             self.buffers = {n: b.detach().clone() for n, b in self.net.named_buffers()}

@@ -20,8 +20,7 @@ import torch
 from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader  # noqa: F401
 from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
 from distributeddataparallel_cifar10_amd.train import TrainConfig, add_cli_args, config_from_args, load_dataset
-from distributeddataparallel_cifar10_amd.train import engine_optimizer, eval_only, eval_source, make_train_loader
-from distributeddataparallel_cifar10_amd.train import resolve_engine
+from distributeddataparallel_cifar10_amd.train import eval_only, make_train_loader, wrap_model
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 
 data_path = '../data/CIFAR-10/'  # reference main_no_ddp.py:17
@@ -42,22 +41,12 @@ def prepare(batch_size=32, pin_memory=False, num_workers=0):
 
 def training_loop(model, train_loader):
     """Reference main_no_ddp.py:36-59 (no checkpoint)."""
-    from distributeddataparallel_cifar10_amd.parallel.ddp import FusedDDPTrainer
-    kind = resolve_engine(_cfg, device, model) if isinstance(model, torch.nn.Module) else None
-    if kind == "fused":
-        n_idx = len(train_loader) * train_loader.batch_size
+    if isinstance(model, torch.nn.Module):
         # one process on a dedicated GPU: the automatic engine choice may give the sliced persistent engine the
         # whole device (batch 64 = 256 step workgroups, one per CU; with one CU kept free it would fall back to the
         # multi-kernel engine: 273.5 vs 97.9 us per step, profiles/bench_b64_r5f.log).  A batch above 64, or a
         # device with fewer CUs, still falls back to the multi-kernel engine with a warning.
-        model = FusedDDPTrainer(model, train_loader.data, train_loader.labels, batch_max=train_loader.batch_size,
-                                lr=_cfg.lr, dtype=_cfg.dtype, max_indices=max(n_idx, train_loader.batch_size),
-                                full_device=True, optimizer=engine_optimizer(_cfg, len(train_loader)),
-                                **eval_source(train_loader))
-    elif kind == "ops":  # the ops-layer HIP kernels (flat parameters, packed weights, HIP SGD)
-        from distributeddataparallel_cifar10_amd.ops.models import OpsModel
-        from distributeddataparallel_cifar10_amd.parallel.flat_ddp import FlatBucketDDP
-        model = FlatBucketDDP(OpsModel(model, fp8=_cfg.fp8), bucket_cap_mb=_cfg.bucket_mb)
+        model = wrap_model(_cfg, model, train_loader, device, full_device=True)
     try:
         return _train_loop(model, train_loader, 0, _cfg)
     finally:

@@ -2,14 +2,15 @@
 the reduction kernel) against the same engine with ``momentum 0.9 + weight decay 5e-4 + cosine table`` (gradient
 reduced unapplied, then ``k_apply_opt``) and against that engine with the pass in its EMA form (``optimizer+ema``:
 decay 0.999, warm-up on) and in its AdamW form (``adamw``: betas (0.9, 0.999), weight decay 5e-2, the same table),
-sliced engine, bf16 and fp32, batch 32, one GPU.
+and that AdamW engine with gradient-norm clipping (``adamw+clip``: ``max_grad_norm`` 0.05, a limit every step exceeds;
+one more kernel, ``k_grad_sqnorm``, in front of the pass's CLIP form), sliced engine, bf16 and fp32, batch 32, one GPU.
 
 One process; the engines of a precision live side by side and are timed in interleaved repetitions (plain, optimiser,
-optimiser + EMA, AdamW, plain, ...), so clock and thermal drift hit all alike.  Each repetition is `--steps` graph-replayed steps between two
+optimiser + EMA, AdamW, AdamW + clip, plain, ...), so clock and thermal drift hit all alike.  Each repetition is `--steps` graph-replayed steps between two
 HIP events recorded on the engine's stream; graphs are captured before the first timed repetition.  Reported: median
 and min / max over the repetitions, and the difference of the medians.
 
-    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32] [--no-ema] [--no-adam]
+    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32] [--no-ema] [--no-adam] [--no-clip]
 """
 from __future__ import annotations
 
@@ -58,6 +59,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--no-ema", action="store_true", help="time plain and optimizer only (A/B against older trees)")
     ap.add_argument("--no-adam", action="store_true", help="leave the adamw engine out (A/B against older trees)")
+    ap.add_argument("--no-clip", action="store_true", help="leave the adamw+clip engine out (A/B against older trees)")
     a = ap.parse_args(argv)
     from distributeddataparallel_cifar10_amd.data.synthetic import synthetic_cifar
     from distributeddataparallel_cifar10_amd.runtime.engine import OptimizerConfig
@@ -79,6 +81,10 @@ def main(argv=None):
         if not a.no_adam:
             adamw = OptimizerConfig(kind="adamw", betas=(0.9, 0.999), weight_decay=5e-2, lr_table=table)
             engines["adamw"] = _engine(dtype, a.batch, adamw, data, labels, order)
+            if not a.no_clip:
+                clip = OptimizerConfig(kind="adamw", betas=(0.9, 0.999), weight_decay=5e-2, lr_table=table,
+                                       max_grad_norm=0.05)
+                engines["adamw+clip"] = _engine(dtype, a.batch, clip, data, labels, order)
         for eng in engines.values():
             _timed(eng, a.batch, a.warmup)
         us = {k: [] for k in engines}
@@ -88,6 +94,10 @@ def main(argv=None):
         for k, eng in engines.items():
             loss, _ = eng.read_loss(reset=True)
             assert np.isfinite(loss), (dtype, k, loss)
+            if k == "adamw+clip":  # the limit did clip
+                norm, clipped = eng.grad_norm()
+                assert clipped > 0, (dtype, norm, clipped)
+                print(f"{dtype} adamw+clip: {clipped} of {total} steps clipped, last norm {norm:.4f}", flush=True)
             eng.close()
         med = {k: statistics.median(v) for k, v in us.items()}
         out[dtype] = {"plain_us": round(med["plain"], 2), "optimizer_us": round(med["optimizer"], 2),
@@ -98,6 +108,9 @@ def main(argv=None):
         if "adamw" in med:
             out[dtype].update(adamw_us=round(med["adamw"], 2),
                               adamw_delta_us=round(med["adamw"] - med["optimizer"], 2))
+        if "adamw+clip" in med:
+            out[dtype].update(clip_us=round(med["adamw+clip"], 2),
+                              clip_delta_us=round(med["adamw+clip"] - med["adamw"], 2))
         for k, v in us.items():
             print(f"{dtype} {k:13s} us/step: median {med[k]:.2f}  min {min(v):.2f}  max {max(v):.2f}  "
                   f"reps {' '.join(f'{x:.2f}' for x in v)}", flush=True)
@@ -109,6 +122,9 @@ def main(argv=None):
         if "adamw" in med:
             print(f"{dtype} AdamW form costs {med['adamw'] - med['optimizer']:+.2f} us/step over optimizer "
                   f"({100 * (med['adamw'] / med['optimizer'] - 1):+.1f} %)", flush=True)
+        if "adamw+clip" in med:
+            print(f"{dtype} clipping costs {med['adamw+clip'] - med['adamw']:+.2f} us/step over adamw "
+                  f"({100 * (med['adamw+clip'] / med['adamw'] - 1):+.1f} %)", flush=True)
     print(json.dumps({"bench": "opt_bench", "engine": "sliced", "batch": a.batch, "steps": a.steps, "reps": a.reps,
                       **out}), flush=True)
 

@@ -10,7 +10,7 @@ operations:
   torch's own) and, with ``--ema-decay``, a ``ModelEma``: an epoch is the reference's step loop.
 
 Operations: ``run_epoch``, ``optimizer_state`` / ``load_optimizer_state``, ``ema_state`` / ``load_ema_state``,
-``evaluate``, ``comm_time``, ``check_comm``; attributes ``engine_name`` and ``fp32_mode`` for the metrics records.
+``evaluate``, ``comm_time``, ``check_comm``, ``grad_norm`` (``--clip-grad-norm``); attributes ``engine_name`` and ``fp32_mode`` for the metrics records.
 The optimiser state travels in the sidecar's own shape: ``{"momentum_buffer": {name: tensor}}`` or ``{"kind",
 "exp_avg": {...}, "exp_avg_sq": {...}}`` (the fused engine adds ``"engine"``, the step kernels' carried state).
 """
@@ -91,6 +91,9 @@ class FusedBackend(_Backend):
                              "(train.engine_optimizer)")
         if cfg.ema_decay is not None and eng.ema is None:
             raise ValueError("--ema-decay is on but the fused trainer was built without it (train.engine_optimizer)")
+        if cfg.clip_grad_norm is not None and eng.clip_part is None:
+            raise ValueError("--clip-grad-norm is on but the fused trainer was built without it "
+                             "(train.engine_optimizer)")
         self.engine_name = eng.kind_name
         self.fp32_mode = ("3xbf16" if eng.kind_name == "sliced" else "fp32-mfma") if cfg.dtype == "fp32" else None
         if cfg.metrics_json:
@@ -129,6 +132,11 @@ class FusedBackend(_Backend):
         if "engine" in state:
             eng.load_step_state(state["engine"])
 
+    def grad_norm(self) -> Optional[tuple]:
+        """``(the last step's gradient norm before clipping, steps clipped since the last call)``, read from the device
+        once per epoch with the loss; None without ``--clip-grad-norm``."""
+        return self.engine.grad_norm(reset=True) if self.cfg.clip_grad_norm is not None else None
+
     def ema_state(self) -> dict:
         return self.engine.ema_state_dict()
 
@@ -153,6 +161,12 @@ class GenericBackend(_Backend):
         self.optimizer = optimizer
         self.opt_state = optimizer if isinstance(optimizer, (FlatSGD, FlatAdam)) else \
             TorchOptimizerState(model, optimizer)
+        # --clip-grad-norm: FlatSGD / FlatAdam clip inside step(); a stock optimiser gets torch's clip_grad_norm_
+        self.clip_torch = cfg.clip_grad_norm is not None and self.opt_state is not optimizer
+        if cfg.clip_grad_norm is not None and not self.clip_torch and optimizer.max_grad_norm is None:
+            raise ValueError("--clip-grad-norm is on but the flat optimiser was built without max_grad_norm "
+                             "(train.make_optimizer)")
+        self._last_norm, self._clipped = 0.0, 0
         self.loss_fn = nn.CrossEntropyLoss()
         on_ops = isinstance(getattr(model, "module", None), OpsModel)
         if on_ops:
@@ -189,10 +203,16 @@ class GenericBackend(_Backend):
             with record_function("backward+allreduce"):
                 loss.backward(_seed_grad(loss))
             with record_function("optimizer"):
+                norm = None
+                if self.clip_torch:
+                    norm = torch.nn.utils.clip_grad_norm_(model.parameters(), self.cfg.clip_grad_norm)
                 optimizer.step()
                 if self.ema is not None:
                     self.ema.update(opt_step + nsteps)
             loss_sum += loss.item()
+            if norm is not None:
+                self._last_norm = float(norm)
+                self._clipped += int(self.cfg.clip_grad_norm / (self._last_norm + 1e-6) < 1.0)
             nsteps += 1
         return self._stepped(loss_sum, nsteps, opt_step)
 
@@ -202,6 +222,15 @@ class GenericBackend(_Backend):
     def load_optimizer_state(self, state: Optional[dict], step: int) -> None:
         if state is not None:
             self.opt_state.load_sidecar_state(state, step)
+
+    def grad_norm(self) -> Optional[tuple]:
+        """As ``FusedBackend.grad_norm``."""
+        if self.cfg.clip_grad_norm is None:
+            return None
+        if not self.clip_torch:
+            return self.optimizer.last_grad_norm(), self.optimizer.clipped_steps(reset=True)
+        out, self._clipped = (self._last_norm, self._clipped), 0
+        return out
 
     def ema_state(self) -> dict:
         return self.ema.state_dict()

@@ -144,6 +144,7 @@ struct Engine {
   OptDev opt{};                 // host mirror of the hyper-parameters (step / ticket live on the device only)
   float* lr_table = nullptr;    // device learning-rate table (owned)
   bool ema_on = false;          // the pass runs in its EMA form (dca_engine_set_ema; opt.ema is then set)
+  bool clip_on = false;         // the pass runs in its CLIP form behind k_grad_sqnorm (dca_engine_set_clip)
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -290,11 +291,12 @@ static int enqueue_xgmi(Engine* e, const Ctx& cx, float* dst, int apply) {
 // The optimiser pass over the flat buffer (momentum, weight decay, the step's learning rate; derived weight copies;
 // CC4 base) -- in place of the step's own SGD when an optimiser is set.
 static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
+  if (e->clip_on) HIPCK(launch_grad_sqnorm(cx, e->opt.part, e->st));  // the CLIP form reads its partials
   if (e->opt.rule != dca::OPT_SGD) {
-    HIPCK(launch_apply_adam(e->bf, e->ema_on, e->opt.rule == dca::OPT_ADAMW, cx, e->optdev, e->st));
+    HIPCK(launch_apply_adam(e->bf, e->ema_on, e->opt.rule == dca::OPT_ADAMW, e->clip_on, cx, e->optdev, e->st));
     return 0;
   }
-  HIPCK(launch_apply_opt(e->bf, e->ema_on, cx, e->optdev, e->st));
+  HIPCK(launch_apply_opt(e->bf, e->ema_on, e->clip_on, cx, e->optdev, e->st));
   return 0;
 }
 
@@ -1053,8 +1055,10 @@ int dca_engine_set_optimizer(void* h, float* momentum_buf, float mu, float wd) {
   const bool on = momentum_buf != nullptr;
   if (on != e->opt_on) drop_graphs(e);
   e->opt_on = false;  // (on again below, once the device block is complete)
-  if (!on) {  // the EMA form and the Adam rule go with the pass
+  if (!on) {  // the EMA form, the CLIP form and the Adam rule go with the pass
     e->ema_on = false;
+    e->clip_on = false;
+    e->opt.part = nullptr;
     e->opt.ema = nullptr;
     e->opt.rule = dca::OPT_SGD;
     e->opt.v = nullptr;
@@ -1145,6 +1149,56 @@ int dca_engine_set_ema(void* h, float* ema_buf, float decay, int warmup) {
   e->opt.ema_warmup = on && warmup ? 1 : 0;
   HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
   e->ema_on = on;
+  return 0;
+}
+
+// CLIP form of the optimiser pass: every update first scales the averaged gradient to a global L2 norm of at most
+// `max_norm` (torch.nn.utils.clip_grad_norm_; optimizer.hip).  `part_buf`: dca_engine_clip_parts() doubles of device
+// memory owned by the caller (8-byte aligned; workspace of the norm kernel).  Needs the optimiser on; null turns the
+// form off.  Switching it on or off drops the captured graphs (one more launch); a new max_norm on a running CLIP form
+// reaches them as it is (device memory).  Synchronous.
+int dca_engine_set_clip(void* h, double* part_buf, float max_norm) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on) {
+    g_err = "set_clip: no optimiser set (dca_engine_set_optimizer first)";
+    return -1;
+  }
+  if (part_buf && !(max_norm > 0.f)) {
+    g_err = "set_clip: max_norm must be positive";
+    return -1;
+  }
+  if (part_buf && ((uintptr_t)part_buf % 8)) {
+    g_err = "set_clip: the partial-sum buffer must be 8-byte aligned";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  const bool on = part_buf != nullptr;
+  if (on != e->clip_on) drop_graphs(e);
+  e->clip_on = false;  // (on again below, once the device block holds the buffer)
+  e->opt.part = part_buf;
+  e->opt.max_norm = on ? max_norm : 0.f;
+  HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
+  e->clip_on = on;
+  return 0;
+}
+
+// Doubles in the workspace dca_engine_set_clip takes.
+int dca_engine_clip_parts(void) { return dca::OPT_PARTS; }
+
+// What the CLIP form recorded: *gnorm <- the last update's gradient norm before clipping (0 before the first),
+// *n_clipped <- updates whose norm exceeded max_norm since the last reset; reset != 0 clears that counter.  Synchronous.
+int dca_engine_clip_state(void* h, double* gnorm, int* n_clipped, int reset) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on || !e->clip_on || !gnorm || !n_clipped) {
+    g_err = "clip_state: clipping is not on (dca_engine_set_clip first)";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  unsigned n = 0;
+  HIPCK(hipMemcpy(gnorm, &e->optdev->gnorm, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(&n, &e->optdev->n_clipped, sizeof(unsigned), hipMemcpyDeviceToHost));
+  *n_clipped = (int)(n & 0x7fffffffu);
+  if (reset) HIPCK(hipMemset(&e->optdev->n_clipped, 0, sizeof(unsigned)));
   return 0;
 }
 

@@ -200,7 +200,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 15; }
+int dca_ops_abi_version() { return 16; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -579,11 +579,14 @@ int dca_ops_dy_prep(const void* dy, int dy_bf16, const void* y, int y_bf16, void
   return 0;
 }
 
-// first: device int (1 on the first momentum step); cleared after the update.
-int dca_ops_sgd(float* p, const float* g, float* buf, long n, float lr, float mu, float wd, int* first, void* stream) {
+// first: device int (1 on the first momentum step); cleared after the update.  gscale: device float the gradient is
+// multiplied by first (dca_ops_clip_coef's coefficient), or null.
+int dca_ops_sgd(float* p, const float* g, float* buf, long n, float lr, float mu, float wd, int* first,
+                const float* gscale, void* stream) {
   REQUIRE(mu == 0.f || buf != nullptr, "sgd: momentum buffer missing");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_sgd, dim3(grid_for(n, 256, 2048)), dim3(256), 0, st, p, g, buf, n, lr, mu, wd, first);
+  auto* k = gscale ? k_sgd<true> : k_sgd<false>;
+  hipLaunchKernelGGL(k, dim3(grid_for(n, 256, 2048)), dim3(256), 0, st, p, g, buf, n, lr, mu, wd, first, gscale);
   if (first) hipLaunchKernelGGL(k_clear_flag, dim3(1), dim3(1), 0, st, first);
   OPCK(hipGetLastError());
   return 0;
@@ -592,9 +595,10 @@ int dca_ops_sgd(float* p, const float* g, float* buf, long n, float lr, float mu
 // Adam (decoupled 0) / AdamW (1) over the flat fp32 slices p / g / m / v of n elements.  state: three device doubles
 // {steps taken, beta1^steps, beta2^steps} ({0, 1, 1} at the start); this update is step `steps taken + 1`.  advance
 // != 0: the state moves on one step after the update (the last -- or only -- update of an optimiser step).  n == 0
-// with advance: the state alone.
+// with advance: the state alone.  gscale: device float the gradient is multiplied by first (dca_ops_clip_coef's
+// coefficient), or null.
 int dca_ops_adam(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, double eps,
-                 float wd, int decoupled, double* state, int advance, void* stream) {
+                 float wd, int decoupled, double* state, int advance, const float* gscale, void* stream) {
   REQUIRE(state != nullptr, "adam: step state missing");
   REQUIRE(n >= 0 && (n == 0 || (p && g && m && v)), "adam: buffer missing");
   REQUIRE(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., "adam: the betas must lie in [0, 1)");
@@ -602,12 +606,31 @@ int dca_ops_adam(float* p, const float* g, float* m, float* v, long n, float lr,
   REQUIRE(wd >= 0.f, "adam: weight decay must not be negative");
   hipStream_t st = (hipStream_t)stream;
   if (n > 0) {
-    auto* k = decoupled ? k_adam<true> : k_adam<false>;
+    auto* k = decoupled ? k_adam<true, false> : k_adam<false, false>;
+    if (gscale) k = decoupled ? k_adam<true, true> : k_adam<false, true>;
     // one float4 per thread up to 512 workgroups (two per CU), grid-stride beyond
     hipLaunchKernelGGL(k, dim3(grid_for((n + 3) / 4, 256, 512)), dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2,
-                       (float)eps, wd, (const double*)state);
+                       (float)eps, wd, (const double*)state, gscale);
   }
   if (advance) hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, st, state, beta1, beta2);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Global gradient-norm clipping of the flat fp32 slice g of n elements (k_sqnorm_part + k_clip_coef): state, 8-byte
+// aligned device memory of dca_ops_clip_state_words() doubles, holds {norm (double), coef (float) | clipped count
+// (uint32)} in its first two words and the partial sums behind them.  The coefficient, for the gscale of dca_ops_sgd /
+// dca_ops_adam, is the float at byte 8.  No host synchronisation.
+int dca_ops_clip_state_words(void) { return 2 + SQN_PARTS; }
+int dca_ops_clip_coef(const float* g, long n, float max_norm, double* state, void* stream) {
+  static_assert(sizeof(ClipState) == 16 && offsetof(ClipState, coef) == 8, "ClipState is the state's first two words");
+  REQUIRE(state != nullptr && ((uintptr_t)state % 8) == 0, "clip_coef: state missing or misaligned");
+  REQUIRE(n >= 0 && (n == 0 || g) && ((uintptr_t)g % 4) == 0, "clip_coef: bad gradient slice");
+  REQUIRE(max_norm > 0.f, "clip_coef: max_norm must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_sqnorm_part, dim3(SQN_PARTS), dim3(256), 0, st, g, n, state + 2);
+  hipLaunchKernelGGL(k_clip_coef, dim3(1), dim3(64), 0, st, (const double*)(state + 2), SQN_PARTS, max_norm,
+                     (ClipState*)state);
   OPCK(hipGetLastError());
   return 0;
 }

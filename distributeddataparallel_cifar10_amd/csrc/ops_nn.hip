@@ -1191,12 +1191,24 @@ __global__ void __launch_bounds__(256) k_dy_prep(const TD* __restrict__ dy, cons
 // ---------------------------------------------------------------------------------------------------------
 // SGD over a flat fp32 buffer, torch.optim.SGD semantics: d = g + wd*p; buf = first ? d : mu*buf + d; p -= lr*buf
 // (mu == 0: no buffer).  `first` is a device flag (the step counter lives on the device: no host sync).
+// SCALE: g is first multiplied by the device float *gscale (the clipping coefficient of k_clip_coef), rounded to
+// fp32 on its own; the form without it is the kernel as it was.
 // ---------------------------------------------------------------------------------------------------------
+// a * b rounded to fp32 on its own: never contracted with an addition that uses it
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+template <bool SCALE>
 __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                             long n, float lr, float mu, float wd, int* __restrict__ first) {
+                                             long n, float lr, float mu, float wd, int* __restrict__ first,
+                                             const float* __restrict__ gscale) {
   const bool init = first ? *first != 0 : false;
+  float gs = 1.f;
+  if constexpr (SCALE) gs = *gscale;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     float d = g[i];
+    if constexpr (SCALE) d = mul_rn(d, gs);
     if (wd != 0.f) d += wd * p[i];
     if (mu != 0.f) {
       d = init ? d : mu * buf[i] + d;
@@ -1217,6 +1229,8 @@ __global__ void k_clear_flag(int* f) { *f = 0; }
 //   p  = p0 - ss * m / (sqrt(v) * c2 + eps),   ss = lr / (1 - beta1^t),  c2 = 1 / sqrt(1 - beta2^t),  t = steps + 1
 // The four slices share their offset from a common base, so they share their alignment: a scalar head up to the first
 // 16-byte boundary of p, float4 accesses over the body, a scalar tail.
+// SCALE: g is first multiplied by the device float *gscale (the clipping coefficient of k_clip_coef), rounded to fp32
+// on its own, before the weight decay; the forms without it are the kernels as they were.
 // ---------------------------------------------------------------------------------------------------------
 struct AdamK {
   float ss, c2, lw, wd, omb1, omb2, beta2, eps;
@@ -1230,11 +1244,14 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   v = __builtin_fmaf(k.beta2, v, (k.omb2 * g) * g);
   p = __builtin_fmaf(-k.ss, m / __builtin_fmaf(__builtin_sqrtf(v), k.c2, k.eps), p0);
 }
-template <bool DECOUPLED>
+template <bool DECOUPLED, bool SCALE>
 __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                               float* __restrict__ v, long n, float lr, double beta1, double beta2,
-                                              float eps, float wd, const double* __restrict__ state) {
+                                              float eps, float wd, const double* __restrict__ state,
+                                              const float* __restrict__ gscale) {
   __shared__ float s_ss, s_c2;
+  float gs = 1.f;
+  if constexpr (SCALE) gs = *gscale;
   if (threadIdx.x == 0) {
     s_ss = (float)((double)lr / (1.0 - state[1] * beta1));
     s_c2 = (float)(1.0 / __builtin_sqrt(1.0 - state[2] * beta2));
@@ -1252,8 +1269,9 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
     const f32x4 gg = *(const f32x4*)(g + e);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float pj = pp[j], mj = mm[j], vj = vv[j];
-      adam_elem<DECOUPLED>(pj, gg[j], mj, vj, k);
+      float pj = pp[j], mj = mm[j], vj = vv[j], gj = gg[j];
+      if constexpr (SCALE) gj = mul_rn(gj, gs);
+      adam_elem<DECOUPLED>(pj, gj, mj, vj, k);
       pp[j] = pj, mm[j] = mj, vv[j] = vj;
     }
     *(f32x4*)(p + e) = pp;
@@ -1264,13 +1282,65 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
   const long nedge = head + (n - tail0);
   for (long i = gid; i < nedge; i += stride) {
     const long e = i < head ? i : tail0 + (i - head);
-    adam_elem<DECOUPLED>(p[e], g[e], m[e], v[e], k);
+    if constexpr (SCALE) adam_elem<DECOUPLED>(p[e], mul_rn(g[e], gs), m[e], v[e], k);
+    else adam_elem<DECOUPLED>(p[e], g[e], m[e], v[e], k);
   }
 }
 __global__ void k_adam_advance(double* state, double beta1, double beta2) {
   state[0] += 1.0;
   state[1] *= beta1;
   state[2] *= beta2;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Global gradient-norm clipping over a flat fp32 slice (torch.nn.utils.clip_grad_norm_, L2), with no host
+// synchronisation, so a captured whole-step graph replays correctly.  Two launches:
+//   k_sqnorm_part: part[b] = workgroup b's sum of (double)g * (double)g (each product exact) over a slice of any start
+//     alignment and length -- scalar head and tail around a float4 body, as k_adam -- on a fixed grid of SQN_PARTS
+//     workgroups; lanes combined by a butterfly, the four waves in order: the same bits on every launch;
+//   k_clip_coef (one workgroup): N = sqrt(sum of the partials in index order), c = (float)(max_norm / (N + 1e-6)),
+//     coef = c < 1 ? c : (c != c ? c : 1) (torch's clamp(max = 1): a NaN stays a NaN); state <- {N, coef, count of the
+//     launches with c < 1}.  k_sgd / k_adam<.., SCALE> multiply g by coef.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int SQN_PARTS = 256;
+struct ClipState {
+  double norm;       // the last norm, before clipping
+  float coef;        // the last coefficient (what gscale points at)
+  unsigned clipped;  // launches that clipped (the host resets it)
+};
+__global__ void __launch_bounds__(256) k_sqnorm_part(const float* __restrict__ g, long n, double* __restrict__ part) {
+  __shared__ double s_w[4];
+  long head = (long)((16 - ((uintptr_t)g & 15)) & 15) / 4;  // scalar elements in front of the first 16-byte boundary
+  if (head > n) head = n;
+  const long n4 = (n - head) >> 2, tail0 = head + 4 * n4;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  double a = 0.;
+  for (long i = gid; i < n4; i += stride) {
+    const f32x4 x = *(const f32x4*)(g + head + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a += (double)x[j] * (double)x[j];
+  }
+  const long nedge = head + (n - tail0);  // fewer than 8 elements
+  for (long i = gid; i < nedge; i += stride) {
+    const double x = (double)g[i < head ? i : tail0 + (i - head)];
+    a += x * x;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+__global__ void __launch_bounds__(64) k_clip_coef(const double* __restrict__ part, int nparts, float max_norm,
+                                                  ClipState* __restrict__ cs) {
+  if (threadIdx.x != 0) return;
+  double s = 0.;
+  for (int i = 0; i < nparts; ++i) s += part[i];
+  const double nrm = __builtin_sqrt(s);
+  const float c = (float)((double)max_norm / (nrm + 1e-6));
+  cs->norm = nrm;
+  cs->coef = c < 1.f ? c : (c != c ? c : 1.f);
+  if (c < 1.f) cs->clipped = cs->clipped + 1u;
 }
 
 // ---------------------------------------------------------------------------------------------------------

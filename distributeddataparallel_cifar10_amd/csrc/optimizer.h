@@ -6,6 +6,10 @@
 
 namespace dca {
 
+constexpr int OPT_V4 = OFF_RS / 4;              // 19019 float4 (every tensor starts 16-byte aligned)
+constexpr int OPT_NB = (OPT_V4 + NT - 1) / NT;  // 75 workgroups, one float4 per thread
+constexpr int OPT_PARTS = OPT_NB;               // doubles in the clipping workspace: one partial per workgroup
+
 struct OptDev {
   const float* lr_table;  // [n_table] per-step learning rates (device), or null
   float* buf;             // momentum buffer, flat fp32 [FLAT_ALLOC] (same layout as params / grads)
@@ -23,11 +27,16 @@ struct OptDev {
   float omb1, omb2;       // (float)(1 - beta1), (float)(1 - beta2), rounded once from the doubles
   float eps;
   int rule;               // OPT_SGD, OPT_ADAM (weight decay as an L2 term), OPT_ADAMW (decoupled)
+  // CLIP forms (dca_engine_set_clip): the averaged gradient is scaled to an L2 norm of at most max_norm
+  float max_norm;         // > 0
+  double* part;           // [OPT_PARTS] k_grad_sqnorm's partial sums of squares (device, owned by the caller), or null
   // ---- everything above is set by the host (copied up to offsetof(OptDev, step)); below: device state ----
   int step;               // optimiser steps taken (device counter)
   unsigned ticket;        // workgroups that have finished reading `step` in the current launch
   double b1p, b2p;        // beta1^step, beta2^step: running products, multiplied once per Adam launch by the workgroup
                           // that advances `step`; the host sets them (adam_products) whenever it sets `step`
+  double gnorm;           // CLIP forms: the last launch's gradient norm, before clipping
+  unsigned n_clipped;     // CLIP forms: launches whose norm exceeded max_norm (the host resets it)
 };
 enum { OPT_SGD = 0, OPT_ADAM = 1, OPT_ADAMW = 2 };
 
@@ -39,10 +48,13 @@ inline double adam_product(double beta, int step) {
   return b;
 }
 
-// Enqueue k_apply_opt<bf, ema> on `st`: one pass over the flat buffer [0, OFF_RS); ema: the form that also updates
-// od->ema (which must then be set).  Returns the launch's hipError_t.
-hipError_t launch_apply_opt(bool bf, bool ema, const Ctx& cx, OptDev* od, hipStream_t st);
-// The same for the Adam forms, k_apply_adam<bf, ema, decoupled> (od->v set, od->rule OPT_ADAM / OPT_ADAMW).
-hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, const Ctx& cx, OptDev* od, hipStream_t st);
+// Enqueue k_apply_opt<bf, ema, clip> on `st`: one pass over the flat buffer [0, OFF_RS); ema: the form that also
+// updates od->ema (which must then be set); clip: the form that scales the gradient by the coefficient it forms from
+// od->part (launch_grad_sqnorm goes first on the same stream).  Returns the launch's hipError_t.
+hipError_t launch_apply_opt(bool bf, bool ema, bool clip, const Ctx& cx, OptDev* od, hipStream_t st);
+// The same for the Adam forms, k_apply_adam<bf, ema, decoupled, clip> (od->v set, od->rule OPT_ADAM / OPT_ADAMW).
+hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, bool clip, const Ctx& cx, OptDev* od, hipStream_t st);
+// Enqueue k_grad_sqnorm: part[OPT_PARTS] <- the partial sums of squares of the averaged gradient in cx.grads.
+hipError_t launch_grad_sqnorm(const Ctx& cx, double* part, hipStream_t st);
 
 }  // namespace dca

@@ -24,21 +24,58 @@
 // EMA compiles to what the pass was before the EMA form existed.
 // The Adam forms (k_apply_adam<BF, EMA, DECOUPLED>; dca_engine_set_adam) are kernels of their own further down: the
 // SGD forms do not change with them.
+// The CLIP forms (k_apply_opt<BF, EMA, true>, k_apply_adam<BF, EMA, DECOUPLED, true>; dca_engine_set_clip) clip the
+// averaged gradient to a global L2 norm first, torch.nn.utils.clip_grad_norm_ before optimizer.step():
+//   x    = fp32(g * inv_ws)
+//   N    = sqrt(sum (double)x * (double)x)   over the 76,074 parameter elements (the CC4 tail and the two pad floats
+//                                            behind fc2.bias are left out by index)
+//   c    = (float)(max_norm / (N + 1e-6))    in double, rounded once
+//   coef = c < 1 ? c : (c != c ? c : 1)      torch's clamp(max = 1): a NaN stays a NaN
+//   x'   = x * coef                          one more fp32 multiplication (never contracted into what follows);
+//                                            coef == 1 leaves x bit for bit
+// and x' takes the place of g * inv_ws above and in the Adam arithmetic below (weight decay is added after clipping).
+// Two launches in stream order: k_grad_sqnorm, the pass's launch shape, writes one double partial per workgroup
+// (every (double)x * (double)x is exact, the partial is a fixed-order wave + LDS reduction: no floating-point
+// atomics); thread 0 of every workgroup of the CLIP form then sums the OPT_NB partials in index order and shares coef
+// through LDS, and thread 0 of workgroup 0 records od->gnorm = N and counts the clipped steps in od->n_clipped.  No
+// grid-wide wait inside one kernel: ranks that share a device must never spin on each other's workgroups.  The forms
+// without CLIP compile to what they were before it existed.
 // A translation unit of its own (see optimizer.h); derive_param comes from netresdeep_kernels.hip.
 #include "netresdeep_kernels.hip"
 #include "optimizer.h"
 
 namespace dca {
 
-constexpr int OPT_V4 = OFF_RS / 4;                  // 19019 float4 (every tensor starts 16-byte aligned)
-constexpr int OPT_NB = (OPT_V4 + NT - 1) / NT;      // 75 workgroups, one float4 per thread
 static_assert(OFF_RS % 4 == 0, "the parameter range must be float4 granular");
+static_assert(OPT_NB * NT >= OPT_V4 && OPT_NB == OPT_PARTS, "one float4 per thread, one partial per workgroup");
 
-template <bool BF, bool EMA>
+// a * b rounded to fp32 on its own: never contracted with an addition that uses it
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// Thread 0 of a CLIP form: the norm from the partials (index order), the coefficient; workgroup 0 records both.
+__device__ __forceinline__ float clip_coef(OptDev* od) {
+  const double* part = od->part;
+  double s = 0.;
+#pragma unroll
+  for (int i = 0; i < OPT_NB; ++i) s += part[i];
+  const double n = __builtin_sqrt(s);
+  const float c = (float)((double)od->max_norm / (n + 1e-6));
+  if (blockIdx.x == 0) {
+    od->gnorm = n;
+    if (c < 1.f) od->n_clipped = od->n_clipped + 1u;
+  }
+  return c < 1.f ? c : (c != c ? c : 1.f);
+}
+
+template <bool BF, bool EMA, bool CLIP>
 __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
   __shared__ float s_lr;
   __shared__ int s_step;
   __shared__ float s_ema;  // (EMA form only: unused, and so not allocated, in the other)
+  __shared__ float s_coef; // (CLIP form only)
   const int t = threadIdx.x, v = blockIdx.x * NT + t;
   if (t == 0) {
     const int st = __hip_atomic_load(&od->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -53,6 +90,7 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
       }
       s_ema = d;
     }
+    if constexpr (CLIP) s_coef = clip_coef(od);
   }
   const float mu = od->mu, wd = od->wd;
   float* mbuf = od->buf;
@@ -60,6 +98,8 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
   if constexpr (EMA) ebuf = od->ema;
   __syncthreads();
   const float lr = s_lr;
+  float coef = 1.f;
+  if constexpr (CLIP) coef = s_coef;
   if (v < OPT_V4) {
     const int e0 = 4 * v;
     const f32x4 g = *(const f32x4*)(cx.grads + e0);
@@ -69,7 +109,9 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
     if constexpr (EMA) a = *(const f32x4*)(ebuf + e0);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float d = __builtin_fmaf(wd, p[k], g[k] * cx.inv_ws);
+      float x = g[k] * cx.inv_ws;
+      if constexpr (CLIP) x = mul_rn(x, coef);
+      const float d = __builtin_fmaf(wd, p[k], x);
       m[k] = __builtin_fmaf(mu, m[k], d);
       p[k] = __builtin_fmaf(-lr, m[k], p[k]);
     }
@@ -116,10 +158,11 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
 // od->b1p = beta1^step, od->b2p = beta2^step (no pow: one multiplication each) and shared as floats.  The workgroup
 // that advances `step` also stores the new products.  The pads between tensors (g = p = m = v = 0) stay exactly 0:
 // m / (0 + eps) = 0.
-template <bool BF, bool EMA, bool DECOUPLED>
+template <bool BF, bool EMA, bool DECOUPLED, bool CLIP>
 __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
   __shared__ float s_lr, s_ss, s_c2;
   __shared__ float s_ema;  // (EMA form only)
+  __shared__ float s_coef; // (CLIP form only)
   const int t = threadIdx.x, v = blockIdx.x * NT + t;
   int st0 = 0;             // thread 0: the step and the products of this launch (t = step + 1)
   double b1t = 0., b2t = 0.;
@@ -141,6 +184,7 @@ __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
       }
       s_ema = d;
     }
+    if constexpr (CLIP) s_coef = clip_coef(od);
   }
   const float wd = od->wd, omb1 = od->omb1, omb2 = od->omb2, beta2 = od->beta2f, eps = od->eps;
   float* mbuf = od->buf;
@@ -149,6 +193,8 @@ __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
   if constexpr (EMA) ebuf = od->ema;
   __syncthreads();
   const float ss = s_ss, c2 = s_c2;
+  float coef = 1.f;
+  if constexpr (CLIP) coef = s_coef;
   if (v < OPT_V4) {
     const int e0 = 4 * v;
     const f32x4 g = *(const f32x4*)(cx.grads + e0);
@@ -162,6 +208,7 @@ __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float gg = g[k] * cx.inv_ws;
+      if constexpr (CLIP) gg = mul_rn(gg, coef);
       float p0 = p[k];
       if constexpr (DECOUPLED) p0 = __builtin_fmaf(-lw, p0, p0);
       else gg = __builtin_fmaf(wd, p0, gg);
@@ -203,20 +250,74 @@ __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
   }
 }
 
-hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, const Ctx& cx, OptDev* od, hipStream_t st) {
-  void (*k)(Ctx, OptDev*) = nullptr;
-#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D>
+// The launchers name the forms without CLIP first, in the order they always had, and the CLIP forms and k_grad_sqnorm
+// behind them: the compiler keeps that order in the code object, so the forms without CLIP stay where they were.
+typedef void (*OptKernel)(Ctx, OptDev*);
+static OptKernel adam_clip_kernel(bool bf, bool ema, bool decoupled);
+static OptKernel opt_clip_kernel(bool bf, bool ema);
+
+hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, bool clip, const Ctx& cx, OptDev* od, hipStream_t st) {
+  OptKernel k = nullptr;
+#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D, false>
   DCA_ADAM(false, false, false); DCA_ADAM(false, false, true); DCA_ADAM(false, true, false); DCA_ADAM(false, true, true);
   DCA_ADAM(true, false, false); DCA_ADAM(true, false, true); DCA_ADAM(true, true, false); DCA_ADAM(true, true, true);
 #undef DCA_ADAM
+  if (clip) k = adam_clip_kernel(bf, ema, decoupled);
   hipLaunchKernelGGL(k, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
   return hipGetLastError();
 }
 
-hipError_t launch_apply_opt(bool bf, bool ema, const Ctx& cx, OptDev* od, hipStream_t st) {
-  auto* k = bf ? k_apply_opt<true, false> : k_apply_opt<false, false>;
-  if (ema) k = bf ? k_apply_opt<true, true> : k_apply_opt<false, true>;
+hipError_t launch_apply_opt(bool bf, bool ema, bool clip, const Ctx& cx, OptDev* od, hipStream_t st) {
+  OptKernel k = bf ? k_apply_opt<true, false, false> : k_apply_opt<false, false, false>;
+  if (ema) k = bf ? k_apply_opt<true, true, false> : k_apply_opt<false, true, false>;
+  if (clip) k = opt_clip_kernel(bf, ema);
   hipLaunchKernelGGL(k, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
+  return hipGetLastError();
+}
+
+static OptKernel adam_clip_kernel(bool bf, bool ema, bool decoupled) {
+  OptKernel k = nullptr;
+#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D, true>
+  DCA_ADAM(false, false, false); DCA_ADAM(false, false, true); DCA_ADAM(false, true, false); DCA_ADAM(false, true, true);
+  DCA_ADAM(true, false, false); DCA_ADAM(true, false, true); DCA_ADAM(true, true, false); DCA_ADAM(true, true, true);
+#undef DCA_ADAM
+  return k;
+}
+
+static OptKernel opt_clip_kernel(bool bf, bool ema) {
+  if (ema) return bf ? k_apply_opt<true, true, true> : k_apply_opt<false, true, true>;
+  return bf ? k_apply_opt<true, false, true> : k_apply_opt<false, false, true>;
+}
+
+// The squared L2 norm of the averaged gradient x = fp32(g * inv_ws) over the parameter elements of cx.grads, as
+// OPT_NB double partials: part[b] is workgroup b's sum, lanes combined by a butterfly within each wave and the four
+// waves in order through LDS -- the same bits on every launch.
+constexpr int OPT_PAD0 = OFF_FC2B + 10;  // 65898, 65899: the two pad floats behind fc2.bias
+// (A template only so that the compiler emits it where it is first named, behind the kernels that were here before.)
+template <int = 0>
+__global__ void __launch_bounds__(NT) k_grad_sqnorm(Ctx cx, double* __restrict__ part) {
+  __shared__ double s_w[NT / 64];
+  const int t = threadIdx.x, v = blockIdx.x * NT + t;
+  double a = 0.;
+  if (v < OPT_V4) {
+    const int e0 = 4 * v;
+    const f32x4 g = *(const f32x4*)(cx.grads + e0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float x = g[k] * cx.inv_ws;
+      const double d = (double)x;
+      if (e0 + k != OPT_PAD0 && e0 + k != OPT_PAD0 + 1) a += d * d;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  if ((t & 63) == 0) s_w[t >> 6] = a;
+  __syncthreads();
+  if (t == 0) part[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+hipError_t launch_grad_sqnorm(const Ctx& cx, double* part, hipStream_t st) {
+  hipLaunchKernelGGL(k_grad_sqnorm<>, dim3(OPT_NB), dim3(NT), 0, st, cx, part);
   return hipGetLastError();
 }
 

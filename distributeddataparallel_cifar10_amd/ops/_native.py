@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 _lock = threading.Lock()
 _lib = None
 
@@ -114,10 +114,15 @@ def _declare(lib):
     lib.dca_ops_dy_prep.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     ctypes.c_long, c_int, c_int, c_int, c_void_p]
     lib.dca_ops_gather_cols.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]
-    lib.dca_ops_sgd.argtypes = [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_void_p, c_void_p]
-    # p, g, m, v, n, lr, beta1, beta2, eps, wd, decoupled, state, advance, stream
+    # p, g, buf, n, lr, mu, wd, first, gscale, stream
+    lib.dca_ops_sgd.argtypes = [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_void_p, c_void_p,
+                                c_void_p]
+    # p, g, m, v, n, lr, beta1, beta2, eps, wd, decoupled, state, advance, gscale, stream
     lib.dca_ops_adam.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, ctypes.c_double,
-                                 ctypes.c_double, ctypes.c_double, c_float, c_int, c_void_p, c_int, c_void_p]
+                                 ctypes.c_double, ctypes.c_double, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p]
+    lib.dca_ops_clip_state_words.argtypes = []
+    lib.dca_ops_clip_state_words.restype = c_int
+    lib.dca_ops_clip_coef.argtypes = [c_void_p, c_long, c_float, c_void_p, c_void_p]  # g, n, max_norm, state, stream
     lib.dca_ops_quant_fp8.argtypes = [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p]
     lib.dca_ops_fp8_alpha.argtypes = [c_void_p, c_void_p, c_float, c_void_p, c_void_p]
     lib.dca_ops_pack_weights.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]

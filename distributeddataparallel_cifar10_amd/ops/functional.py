@@ -1216,14 +1216,61 @@ def cross_entropy(logits, labels):
 # SGD over flat fp32 buffers (torch.optim.SGD semantics incl. momentum's first-step buffer init)
 # ------------------------------------------------------------------------------------------------------------
 def sgd_step_(p: torch.Tensor, g: torch.Tensor, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
-              buf: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None) -> None:
+              buf: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
+              gscale: Optional[torch.Tensor] = None) -> None:
+    """``gscale``: a one-element fp32 device tensor the gradient is multiplied by first (``clip_scale``), or None."""
     _dev_check(p, g, buf)
+    _check_gscale(gscale, p)
     if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
         raise TypeError("sgd_step_: contiguous fp32 buffers")
     if momentum and buf is None:
         raise ValueError("sgd_step_: momentum needs a buffer")
     N.check(N.lib().dca_ops_sgd(N.ptr(p), N.ptr(g), N.ptr(buf), p.numel(), float(lr), float(momentum),
-                                float(weight_decay), N.ptr(first), N.stream(p.device)), "sgd")
+                                float(weight_decay), N.ptr(first), N.ptr(gscale), N.stream(p.device)), "sgd")
+
+
+def _check_gscale(gscale, p) -> None:
+    if gscale is not None and (gscale.dtype != torch.float32 or gscale.numel() != 1 or gscale.device != p.device):
+        raise TypeError("gscale: one fp32 element on the parameters' device (clip_scale)")
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Global gradient-norm clipping over a flat fp32 buffer (torch.nn.utils.clip_grad_norm_; utils/schedule.py
+# clip_reference): the coefficient is formed on the device and handed to sgd_step_ / adam_step_ as `gscale`
+# ------------------------------------------------------------------------------------------------------------
+def clip_state(device) -> torch.Tensor:
+    """A fresh state of ``clip_coef_``: float64 words on `device` -- word 0 the last norm, word 1 the last coefficient
+    (fp32) and the count of clipping calls (uint32), the rest the norm kernel's partial sums."""
+    return torch.zeros(int(N.lib().dca_ops_clip_state_words()), dtype=torch.float64, device=device)
+
+
+def clip_scale(state: torch.Tensor) -> torch.Tensor:
+    """The coefficient of the last ``clip_coef_`` as a one-element fp32 view of `state`: the ``gscale`` of the update."""
+    return state.view(torch.float32)[2:3]
+
+
+def clip_readout(state: torch.Tensor, reset: bool = False) -> tuple:
+    """``(last norm, clipping calls since the last reset)`` of a ``clip_coef_`` state.  Synchronises."""
+    head = state[:2].cpu()
+    if reset:
+        state.view(torch.int32)[3:4].zero_()
+    return float(head[0]), int(head.view(torch.int32)[3])
+
+
+def clip_coef_(grad: torch.Tensor, max_norm: float, state: torch.Tensor) -> torch.Tensor:
+    """The global L2 norm of the flat fp32 slice `grad` (any start alignment and length) and the clipping coefficient
+    ``min(1, max_norm / (norm + 1e-6))`` for it, written to `state` (``clip_state``) with no host synchronisation;
+    `grad` itself is not changed.  Returns ``clip_scale(state)``."""
+    _dev_check(grad, state)
+    if grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise TypeError("clip_coef_: a contiguous fp32 buffer")
+    if state.dtype != torch.float64 or not state.is_contiguous() or \
+            state.numel() != int(N.lib().dca_ops_clip_state_words()):
+        raise TypeError("clip_coef_: the state comes from clip_state()")
+    from ..utils.schedule import check_max_norm
+    N.check(N.lib().dca_ops_clip_coef(N.ptr(grad), grad.numel(), check_max_norm(max_norm), N.ptr(state),
+                                      N.stream(grad.device)), "clip_coef")
+    return clip_scale(state)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1247,11 +1294,13 @@ def adam_state_at(step: int, beta1: float, beta2: float, device) -> torch.Tensor
 
 def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor, lr: float,
                betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = True,
-               advance: bool = True) -> None:
+               advance: bool = True, gscale: Optional[torch.Tensor] = None) -> None:
     """One Adam (``decoupled=False``) / AdamW update of the flat fp32 slice `p` in place from its gradient `g`, with
     the moments `m` and `v` (zero at the start), as step ``state[0] + 1`` (``adam_state``).  ``advance=False`` leaves
-    the state where it is -- for all but the last of several slices updated in one optimiser step."""
+    the state where it is -- for all but the last of several slices updated in one optimiser step.  ``gscale``: a
+    one-element fp32 device tensor the gradient is multiplied by first (``clip_scale``), or None."""
     _dev_check(p, g, m, v, state)
+    _check_gscale(gscale, p)
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
             raise TypeError("adam_step_: contiguous fp32 buffers of one length")
@@ -1261,10 +1310,10 @@ def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     check_adam(betas[0], betas[1], eps, weight_decay)
     N.check(N.lib().dca_ops_adam(N.ptr(p), N.ptr(g), N.ptr(m), N.ptr(v), p.numel(), float(lr), float(betas[0]),
                                  float(betas[1]), float(eps), float(weight_decay), 1 if decoupled else 0, N.ptr(state),
-                                 1 if advance else 0, N.stream(p.device)), "adam")
+                                 1 if advance else 0, N.ptr(gscale), N.stream(p.device)), "adam")
 
 
 def adam_advance_(state: torch.Tensor, betas) -> None:
     """Move an ``adam_step_`` state on one step without an update (after slices updated with ``advance=False``)."""
     N.check(N.lib().dca_ops_adam(None, None, None, None, 0, 0.0, float(betas[0]), float(betas[1]), 1.0, 0.0, 0,
-                                 N.ptr(state), 1, N.stream(state.device)), "adam")
+                                 N.ptr(state), 1, None, N.stream(state.device)), "adam")

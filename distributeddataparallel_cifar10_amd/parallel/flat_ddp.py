@@ -354,7 +354,62 @@ class FlatBucketDDP(nn.Module):
             self.xgmi = None
 
 
-class FlatSGD(torch.optim.Optimizer):
+class _GradClip:
+    """Global gradient-norm clipping of the flat gradient for ``FlatSGD`` / ``FlatAdam``
+    (``torch.nn.utils.clip_grad_norm_``; ``utils/schedule.py clip_reference`` is the rule).  On a GPU the norm and the
+    coefficient are formed on the device (``ops/functional.py clip_coef_``) and the update kernel multiplies the
+    gradient by the coefficient, with no host synchronisation; on the CPU it is torch ops on ``flat_grad``."""
+
+    def _init_clip(self, max_grad_norm, overlap: bool) -> None:
+        if max_grad_norm is not None:
+            from ..utils.schedule import check_max_norm
+            max_grad_norm = check_max_norm(max_grad_norm)
+            if overlap:
+                raise ValueError("max_grad_norm cannot be combined with overlap=True: a bucket cannot be updated "
+                                 "before the norm of all buckets is known")
+        self.max_grad_norm = max_grad_norm
+        self._clip_state = None   # GPU: the device state of clip_coef_
+        self._last_norm = 0.0     # CPU: the last norm and the clipped steps
+        self._clipped = 0
+
+    @torch.no_grad()
+    def _clip(self):
+        """Before an update: GPU -> the ``gscale`` tensor of the update kernel; CPU -> ``flat_grad`` scaled in place
+        (None).  None without a limit."""
+        if self.max_grad_norm is None:
+            return None
+        grad = self.ddp.flat_grad
+        if grad.is_cuda:
+            from ..ops.functional import clip_coef_, clip_state
+            if self._clip_state is None:
+                self._clip_state = clip_state(grad.device)
+            return clip_coef_(grad, self.max_grad_norm, self._clip_state)
+        norm = grad.norm()
+        coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+        grad.mul_(coef)
+        self._last_norm = float(norm)
+        self._clipped += int(float(coef) < 1.0)
+        return None
+
+    def last_grad_norm(self) -> float:
+        """The L2 norm of the last step's gradient before clipping (0.0 before the first).  GPU: synchronises."""
+        if self._clip_state is not None:
+            from ..ops.functional import clip_readout
+            return clip_readout(self._clip_state)[0]
+        return self._last_norm
+
+    def clipped_steps(self, reset: bool = False) -> int:
+        """Steps whose norm exceeded the limit since the last reset.  GPU: synchronises."""
+        if self._clip_state is not None:
+            from ..ops.functional import clip_readout
+            return clip_readout(self._clip_state, reset)[1]
+        n = self._clipped
+        if reset:
+            self._clipped = 0
+        return n
+
+
+class FlatSGD(_GradClip, torch.optim.Optimizer):
     """``optim.SGD`` over the flat buffer in one or two fused ops.
 
     Default = reference ``main.py:27`` (lr only).  ``momentum`` / ``weight_decay`` follow torch.optim.SGD's
@@ -363,11 +418,15 @@ class FlatSGD(torch.optim.Optimizer):
     ``overlap=True`` (BASELINE config 5, "fused SGD + all-reduce overlap"): every gradient bucket is updated as
     soon as it is complete -- right behind its all-reduce on the comm stream (HIP SGD kernel), or on a side
     stream with one rank -- so the update overlaps the rest of the backward; ``step()`` then has nothing left
-    to do.  The momentum buffer starts at zero, so its first update equals the gradient (torch's semantics)."""
+    to do.  The momentum buffer starts at zero, so its first update equals the gradient (torch's semantics).
+
+    ``max_grad_norm``: ``step()`` first clips the flat gradient to this global L2 norm (``_GradClip``; not with
+    ``overlap``); ``last_grad_norm()`` / ``clipped_steps()`` report it."""
 
     def __init__(self, ddp: FlatBucketDDP, lr: float = 1e-2, momentum: float = 0.0, weight_decay: float = 0.0,
-                 overlap: bool = False):
+                 overlap: bool = False, max_grad_norm: Optional[float] = None):
         super().__init__(list(ddp.module.parameters()), dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        self._init_clip(max_grad_norm, overlap)
         self.ddp = ddp
         self._buf = None    # the flat momentum buffer; None before the first momentum step
         self._first = None  # GPU: the HIP kernel's "buffer not initialised yet" flag (an int32 on the device)
@@ -400,13 +459,14 @@ class FlatSGD(torch.optim.Optimizer):
         if self.overlap:  # already applied bucket by bucket during the backward
             return loss
         g = self.param_groups[0]
+        gscale = self._clip()
         if self.ddp.flat.is_cuda:  # one HIP kernel over the flat buffer (ops/functional.py sgd_step_)
             from ..ops.functional import sgd_step_
             if g["momentum"] and self._buf is None:
                 self._buf = torch.empty_like(self.ddp.flat)
                 self._first = torch.ones(1, dtype=torch.int32, device=self.ddp.flat.device)
             sgd_step_(self.ddp.flat, self.ddp.flat_grad, g["lr"], g["momentum"], g["weight_decay"], buf=self._buf,
-                      first=self._first)
+                      first=self._first, gscale=gscale)
             return loss
         grad = self.ddp.flat_grad
         if g["weight_decay"]:
@@ -442,18 +502,20 @@ class FlatSGD(torch.optim.Optimizer):
             view.copy_(bufs[name])
 
 
-class FlatAdam(torch.optim.Optimizer):
+class FlatAdam(_GradClip, torch.optim.Optimizer):
     """``optim.AdamW`` (``decoupled=True``, the default) or ``optim.Adam`` (``False``: weight decay as an L2 term of
     the gradient) over the flat buffer, amsgrad off -- ``utils/schedule.py adam_reference`` is the rule.  On a GPU the
     update is one HIP kernel (``ops/functional.py adam_step_``) and the step counter with its bias-correction products
     lives in device memory, so a captured whole-step graph replays correctly; on the CPU it is torch ops in the order
     of torch's own implementation.  ``overlap=True``: as for ``FlatSGD``, every gradient bucket is updated as soon as
-    it is reduced and ``step()`` only moves the step counter on."""
+    it is reduced and ``step()`` only moves the step counter on.  ``max_grad_norm``: as for ``FlatSGD``."""
 
     def __init__(self, ddp: FlatBucketDDP, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, decoupled: bool = True, overlap: bool = False):
+                 weight_decay: float = 0.0, decoupled: bool = True, overlap: bool = False,
+                 max_grad_norm: Optional[float] = None):
         from ..utils.schedule import check_adam
         check_adam(betas[0], betas[1], eps, weight_decay)
+        self._init_clip(max_grad_norm, overlap)
         if ddp.flat.dtype != torch.float32:
             raise TypeError("FlatAdam: fp32 parameters")
         super().__init__(list(ddp.module.parameters()),
@@ -487,14 +549,15 @@ class FlatAdam(torch.optim.Optimizer):
         self._t = int(step)
 
     @torch.no_grad()
-    def _update_slice(self, s: int, e: int, advance: bool = False) -> None:
+    def _update_slice(self, s: int, e: int, advance: bool = False, gscale=None) -> None:
         g = self.param_groups[0]
         p, grad = self.ddp.flat[s:e], self.ddp.flat_grad[s:e]
         m, v = self.exp_avg[s:e], self.exp_avg_sq[s:e]
         (b1, b2), lr, eps, wd = g["betas"], g["lr"], g["eps"], g["weight_decay"]
         if p.is_cuda:
             from ..ops.functional import adam_step_
-            adam_step_(p, grad, m, v, self._state, lr, (b1, b2), eps, wd, decoupled=self.decoupled, advance=advance)
+            adam_step_(p, grad, m, v, self._state, lr, (b1, b2), eps, wd, decoupled=self.decoupled, advance=advance,
+                       gscale=gscale)
             return
         t = self._t + 1  # (the order of torch/optim/adam.py _single_tensor_adam)
         if wd:
@@ -515,7 +578,7 @@ class FlatAdam(torch.optim.Optimizer):
                 from ..ops.functional import adam_advance_
                 adam_advance_(self._state, self.param_groups[0]["betas"])
         else:
-            self._update_slice(0, self.ddp.flat.numel(), advance=True)
+            self._update_slice(0, self.ddp.flat.numel(), advance=True, gscale=self._clip())
         self._t += 1
         return loss
 

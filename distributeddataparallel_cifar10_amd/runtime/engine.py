@@ -136,7 +136,9 @@ class OptimizerConfig:
     (``utils/ema.py``; ``ema_warmup``: decay ``min(ema_decay, (1 + k) / (10 + k))`` at step k); ``None``: no average.
     ``kind``: ``"sgd"`` (the above), or ``"adam"`` / ``"adamw"`` -- torch ``Adam`` / ``AdamW`` (amsgrad off) with
     ``betas`` and ``eps``, the pass's Adam forms; ``weight_decay`` is then an L2 term of the gradient (``adam``) or
-    decoupled (``adamw``), and ``momentum`` must be 0 (``utils/schedule.py adam_reference`` is the rule)."""
+    decoupled (``adamw``), and ``momentum`` must be 0 (``utils/schedule.py adam_reference`` is the rule).
+    ``max_grad_norm``: every update first scales the averaged gradient to a global L2 norm of at most this value
+    (``torch.nn.utils.clip_grad_norm_``; ``utils/schedule.py clip_reference`` is the rule); ``None``: no clipping."""
     momentum: float = 0.0
     weight_decay: float = 0.0
     lr_table: Optional[Sequence[float]] = None
@@ -145,6 +147,7 @@ class OptimizerConfig:
     kind: str = "sgd"
     betas: Sequence[float] = (0.9, 0.999)
     eps: float = 1e-8
+    max_grad_norm: Optional[float] = None
 
 
 OPTIMIZER_KINDS = ("sgd", "adam", "adamw")
@@ -163,6 +166,9 @@ def check_optimizer_config(opt: OptimizerConfig) -> None:
         if len(opt.betas) != 2:
             raise ValueError("betas must be (beta1, beta2)")
         check_adam(opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay)
+    if opt.max_grad_norm is not None:
+        from ..utils.schedule import check_max_norm
+        check_max_norm(opt.max_grad_norm)
 
 
 def optimizer_state_kind(state: dict) -> str:
@@ -278,6 +284,7 @@ class NetResDeepEngine:
         self.momentum = None  # flat fp32 momentum buffer (optimiser mode), laid out like `flat` and `grads`
         self.ema = None  # flat fp32 [FLAT_ALLOC] average (EMA on), laid out like `grads`: running stats at OFF_RS
         self.exp_avg_sq = None  # flat fp32 second moment (an Adam kind; `momentum` is then the first moment)
+        self.clip_part = None  # float64 partial sums of the gradient-norm kernel (clipping on)
         if cfg.optimizer is not None:
             self.set_optimizer(cfg.optimizer)
 
@@ -288,7 +295,8 @@ class NetResDeepEngine:
         if opt is None:
             native.check(self.lib.dca_engine_set_optimizer(self.h, None, 0.0, 0.0), "dca_engine_set_optimizer")
             self.cfg.optimizer = None
-            self.ema = None  # (the EMA form and the Adam rule go with the pass)
+            self.ema = None  # (the EMA form, clipping and the Adam rule go with the pass)
+            self.clip_part = None
             return
         check_optimizer_config(opt)
         adam = opt.kind != "sgd"
@@ -312,6 +320,8 @@ class NetResDeepEngine:
             self.set_lr_table(opt.lr_table)
         if opt.ema_decay is not None or self.ema is not None:
             self.set_ema_decay(opt.ema_decay, opt.ema_warmup)
+        if opt.max_grad_norm is not None or self.clip_part is not None:
+            self.set_max_grad_norm(opt.max_grad_norm)
 
     def set_lr_table(self, values) -> None:
         """Per-step learning rates: optimiser step k uses ``values[min(k, len - 1)]``; an empty table returns to the
@@ -453,6 +463,43 @@ class NetResDeepEngine:
                     raise ValueError(f"{name}: expected shape {tuple(view.shape)}, got {tuple(t.shape)}")
                 view.copy_(t.detach().to(self.device, torch.float32))
         torch.cuda.synchronize(self.device)
+
+    # ---- gradient-norm clipping (the optimiser pass's CLIP form) ----------------------------------------------
+    def set_max_grad_norm(self, max_norm: Optional[float]) -> None:
+        """A new limit for the global L2 norm of the averaged gradient.  On an engine that clips already the captured
+        step graphs pick it up without re-capture; on one that does not this switches clipping on (one more kernel per
+        step), and ``None`` switches it off -- either switch drops the captured graphs."""
+        from ..utils.schedule import check_max_norm
+        self._need_optimizer()
+        opt = self.cfg.optimizer
+        if max_norm is None:
+            native.check(self.lib.dca_engine_set_clip(self.h, None, 0.0), "dca_engine_set_clip")
+            self.clip_part, opt.max_grad_norm = None, None
+            return
+        max_norm = check_max_norm(max_norm)
+        fresh = self.clip_part is None
+        if fresh:
+            self.clip_part = torch.zeros(int(self.lib.dca_engine_clip_parts()), dtype=torch.float64, device=self.device)
+            torch.cuda.synchronize(self.device)
+        try:
+            native.check(self.lib.dca_engine_set_clip(self.h, self.clip_part.data_ptr(), max_norm),
+                         "dca_engine_set_clip")
+        except RuntimeError:
+            if fresh:
+                self.clip_part = None
+            raise
+        opt.max_grad_norm = max_norm
+
+    def grad_norm(self, reset: bool = False) -> tuple[float, int]:
+        """``(last_norm, clipped_steps)``: the L2 norm of the last step's averaged gradient before clipping (0.0 before
+        the first step) and the number of steps whose norm exceeded the limit since the counter was last reset
+        (``reset=True`` clears it after reading).  Needs clipping on.  Synchronises."""
+        if self.clip_part is None:
+            raise RuntimeError("no clipping: OptimizerConfig(max_grad_norm=...) or set_max_grad_norm()")
+        n, c = ctypes.c_double(), ctypes.c_int()
+        native.check(self.lib.dca_engine_clip_state(self.h, ctypes.byref(n), ctypes.byref(c), 1 if reset else 0),
+                     "dca_engine_clip_state")
+        return float(n.value), int(c.value)
 
     # ---- carried step state ---------------------------------------------------------------------------------
     def step_state(self) -> dict:

@@ -88,6 +88,11 @@ def _declare(lib):
     lib.dca_engine_set_ema.argtypes = [c_void_p, c_void_p, ctypes.c_float, c_int]  # handle, buffer, decay, warm-up
     # handle, second-moment buffer, beta1, beta2, eps, decoupled
     lib.dca_engine_set_adam.argtypes = [c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int]
+    lib.dca_engine_set_clip.argtypes = [c_void_p, c_void_p, ctypes.c_float]  # handle, partial-sum buffer, max_norm
+    lib.dca_engine_clip_parts.argtypes = []
+    lib.dca_engine_clip_parts.restype = c_int
+    # handle, norm out, clipped-steps out, reset
+    lib.dca_engine_clip_state.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), c_int]
     lib.dca_eval_netresdeep.argtypes = [c_void_p, c_void_p]  # DcaEvalArgs*, hipStream_t (runtime/evaluate.py)
     # csrc/augment.hip (data/augment.py): src, dst, ids, n, n_rows, seed, epoch, pad, flip, hipStream_t; no engine
     # handle, and an error string of its own

@@ -90,6 +90,7 @@ class TrainConfig:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_eps: float = 1e-8
+    clip_grad_norm: Optional[float] = None  # None: off; X > 0: clip the gradient's global L2 norm to X before each update
     extra: dict = field(default_factory=dict)
 
 
@@ -154,6 +155,10 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--adam-beta2", type=float, default=_D.adam_beta2,
                     help="Adam / AdamW: second-moment decay, in [0, 1)")
     ap.add_argument("--adam-eps", type=float, default=_D.adam_eps, help="Adam / AdamW: the denominator's epsilon, > 0")
+    ap.add_argument("--clip-grad-norm", type=float, default=_D.clip_grad_norm, metavar="X",
+                    help="before every optimiser step, scale the (averaged) gradient so that its global L2 norm is at "
+                         "most X > 0, as torch.nn.utils.clip_grad_norm_; the metrics record the norm and the number of "
+                         "clipped steps (default: off)")
     ap.add_argument("--lr-schedule", default=_D.lr_schedule, choices=["constant", "step", "cosine"],
                     help="per-step learning-rate schedule over epochs x steps-per-epoch steps (default: constant --lr)")
     ap.add_argument("--lr-warmup-steps", type=int, default=_D.lr_warmup_steps,
@@ -204,6 +209,8 @@ def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConf
         cfg.eval = 0
     if cfg.ema_decay is not None and not 0.0 <= cfg.ema_decay < 1.0:
         raise SystemExit("--ema-decay must lie in [0, 1)")
+    if cfg.clip_grad_norm is not None and not cfg.clip_grad_norm > 0.0:
+        raise SystemExit("--clip-grad-norm must be positive")
     if cfg.optimizer != "sgd":  # values no Adam takes
         if cfg.momentum:
             raise SystemExit(f"--momentum belongs to --optimizer sgd; --optimizer {cfg.optimizer} takes --adam-beta1 / "
@@ -221,9 +228,10 @@ def optimizer_active(cfg: TrainConfig) -> bool:
     its own fused SGD (``optimizer=None``) and the other engines build FlatSGD(model, lr) / torch.optim.SGD(lr).
     ``--ema-decay`` alone turns it on too: the fused engine keeps the average in its optimiser pass, so it then takes
     the split step form (with a constant table if no schedule is given).  So does ``--optimizer adam`` / ``adamw``:
-    the Adam rule is a form of that pass."""
+    the Adam rule is a form of that pass.  And so does ``--clip-grad-norm``: the norm needs the whole reduced gradient
+    before any of it is applied, which is the split form plus one more kernel in front of the pass."""
     return bool(cfg.momentum or cfg.weight_decay or cfg.lr_schedule is not None or cfg.lr_warmup_steps
-                or cfg.ema_decay is not None or cfg.optimizer != "sgd")
+                or cfg.ema_decay is not None or cfg.optimizer != "sgd" or cfg.clip_grad_norm is not None)
 
 
 def steps_per_epoch_of(cfg: TrainConfig, n_batches: int) -> int:
@@ -252,7 +260,8 @@ def engine_optimizer(cfg: TrainConfig, n_batches: int):
     from .runtime.engine import OptimizerConfig
     return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table,
                            ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup, kind=cfg.optimizer,
-                           betas=(cfg.adam_beta1, cfg.adam_beta2), eps=cfg.adam_eps)
+                           betas=(cfg.adam_beta1, cfg.adam_beta2), eps=cfg.adam_eps,
+                           max_grad_norm=cfg.clip_grad_norm)
 
 
 def augment_config(cfg: TrainConfig):
@@ -287,7 +296,7 @@ def make_adam(model, cfg: TrainConfig):
     betas = (cfg.adam_beta1, cfg.adam_beta2)
     if isinstance(model, FlatBucketDDP):
         return FlatAdam(model, cfg.lr, betas=betas, eps=cfg.adam_eps, weight_decay=cfg.weight_decay,
-                        decoupled=cfg.optimizer == "adamw")
+                        decoupled=cfg.optimizer == "adamw", max_grad_norm=cfg.clip_grad_norm)
     cls = torch.optim.AdamW if cfg.optimizer == "adamw" else torch.optim.Adam
     return cls(model.parameters(), lr=cfg.lr, betas=betas, eps=cfg.adam_eps, weight_decay=cfg.weight_decay)
 
@@ -302,7 +311,11 @@ def make_optimizer(model, cfg: TrainConfig, table):
     if cfg.optimizer != "sgd":
         return make_adam(model, cfg)
     args = dict(momentum=cfg.momentum, weight_decay=cfg.weight_decay)
-    return flat_ddp.FlatSGD(model, cfg.lr, **args) if flat else torch.optim.SGD(model.parameters(), lr=cfg.lr, **args)
+    if flat:
+        if cfg.clip_grad_norm is not None:  # (passed only when set: the default call stays what it was)
+            args["max_grad_norm"] = cfg.clip_grad_norm
+        return flat_ddp.FlatSGD(model, cfg.lr, **args)
+    return torch.optim.SGD(model.parameters(), lr=cfg.lr, **args)
 
 
 _STATE_TENSORS = ("momentum_buffer", "exp_avg", "exp_avg_sq")  # the sidecar's {parameter name: tensor} entries
@@ -472,6 +485,7 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
         mean = loss_sum / n_batches  # reference divides by len(train_loader) (main.py:44)
         history.append(mean)
         comm_us, comm_n = backend.comm_time() if cfg.metrics_json else (0.0, 0)
+        clip = backend.grad_norm()  # --clip-grad-norm: (the last step's norm, the epoch's clipped steps), else None
         ev = ema_ev = None
         ev_rec = {}
         if eval_set is not None and (should_log(epoch) or epoch == cfg.epochs):
@@ -490,6 +504,9 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                    # the decay of the epoch's last EMA update
                    ema_decay=ema_decay_at(opt_step - 1, cfg.ema_decay, cfg.ema_warmup)
                    if cfg.ema_decay is not None and opt_step > 0 else None,
+                   # the last step's gradient norm before clipping, the epoch's clipped steps, the limit
+                   grad_norm=clip[0] if clip else None, clipped_steps=clip[1] if clip else None,
+                   clip_grad_norm=cfg.clip_grad_norm,
                    dtype=cfg.dtype, fp32_mode=backend.fp32_mode, **ev_rec)
         if should_log(epoch):
             print(epoch_line(epoch, mean), flush=True)

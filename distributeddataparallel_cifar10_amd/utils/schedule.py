@@ -113,6 +113,46 @@ def adam_reference(p, g, m, v, t: int, lr: float, beta1: float, beta2: float, ep
     return p0 - (lr / (1.0 - b1 ** t)) * nm / denom, nm, nv
 
 
+def check_max_norm(max_norm) -> float:
+    """The limit of gradient-norm clipping as a float: ValueError unless it is positive (a NaN is not)."""
+    try:
+        v = float(max_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"the gradient-norm limit must be a positive number, got {max_norm!r}") from None
+    if not v > 0.0:
+        raise ValueError(f"the gradient-norm limit must be positive, got {max_norm!r}")
+    return v
+
+
+def clip_reference(grads, max_norm: float, inv_ws: float = 1.0):
+    """Global gradient-norm clipping in float64 -- ``torch.nn.utils.clip_grad_norm_`` (L2, ``error_if_nonfinite``
+    off), the oracle of ``k_grad_sqnorm`` + the CLIP forms of the optimiser pass, of ``k_sqnorm_part`` + ``k_clip_coef``
+    and of the flat optimisers' CPU path.  `grads`: one array / tensor or a sequence of them (the summed gradients):
+
+        x = g * inv_ws  (rounded to fp32 where g is fp32: the averaged gradient as the kernels form it)
+        N = sqrt(sum x * x)  in float64;   c = fp32(max_norm / (N + 1e-6))
+        coef = c if c < 1 else (c if c != c else 1)      (torch's clamp(max=1): a NaN stays a NaN)
+
+    Returns ``(N, coef)``: a Python float and a ``numpy.float32``; the clipped averaged gradient is ``x * coef`` (one
+    more fp32 rounding on the device), and that is what ``sgd_reference`` / ``adam_reference`` then receive."""
+    max_norm = check_max_norm(max_norm)
+    if hasattr(grads, "detach") or isinstance(grads, np.ndarray):
+        grads = [grads]
+    total = 0.0
+    for g in grads:
+        is32 = (hasattr(g, "detach") and str(g.dtype) == "torch.float32") or getattr(g, "dtype", None) == np.float32
+        x = _f64(g).reshape(-1) * float(inv_ws)
+        if is32:
+            with np.errstate(over="ignore", invalid="ignore"):
+                x = x.astype(np.float32).astype(np.float64)
+        total += float(np.sum(x * x))
+    norm = math.sqrt(total) if total == total else float("nan")
+    with np.errstate(over="ignore", invalid="ignore"):
+        c = np.float32(np.float64(max_norm) / (np.float64(norm) + 1e-6))
+    coef = c if c < np.float32(1.0) else (c if c != c else np.float32(1.0))
+    return norm, np.float32(coef)
+
+
 def _f64(x) -> np.ndarray:
     if hasattr(x, "detach"):
         x = x.detach().cpu().double().numpy()

@@ -1,5 +1,6 @@
 """Unit tests of the ops-layer HIP kernels (csrc/ops_*.hip) against plain PyTorch fp32 references of the same op
-(layer 1: one test family per kernel family, random + ragged shapes, asymmetric operands)."""
+(layer 1: one test family per kernel family, random + ragged shapes, asymmetric operands).
+The exact, per-element tests of the same kernels are tests/test_ops_nn_forms_gpu.py and tests/test_ops_conv_dgrad_gpu.py."""
 import os
 
 import pytest

@@ -3,14 +3,17 @@ the reduction kernel) against the same engine with ``momentum 0.9 + weight decay
 reduced unapplied, then ``k_apply_opt``) and against that engine with the pass in its EMA form (``optimizer+ema``:
 decay 0.999, warm-up on) and in its AdamW form (``adamw``: betas (0.9, 0.999), weight decay 5e-2, the same table),
 and that AdamW engine with gradient-norm clipping (``adamw+clip``: ``max_grad_norm`` 0.05, a limit every step exceeds;
-one more kernel, ``k_grad_sqnorm``, in front of the pass's CLIP form), sliced engine, bf16 and fp32, batch 32, one GPU.
+one more kernel, ``k_grad_sqnorm``, in front of the pass's CLIP form), and the AdamW engine with gradient accumulation
+(``adamw+accum4``: ``accumulate_steps`` 4; one more kernel, ``k_grad_accum``, in front of the pass's ACC form, which
+applies an update on every fourth micro-step only; reported per micro-step), sliced engine, bf16 and fp32, batch 32,
+one GPU.
 
 One process; the engines of a precision live side by side and are timed in interleaved repetitions (plain, optimiser,
 optimiser + EMA, AdamW, AdamW + clip, plain, ...), so clock and thermal drift hit all alike.  Each repetition is `--steps` graph-replayed steps between two
 HIP events recorded on the engine's stream; graphs are captured before the first timed repetition.  Reported: median
 and min / max over the repetitions, and the difference of the medians.
 
-    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32] [--no-ema] [--no-adam] [--no-clip]
+    python bench/opt_bench.py [--steps 320] [--reps 9] [--batch 32] [--no-ema] [--no-adam] [--no-clip] [--no-accum]
 """
 from __future__ import annotations
 
@@ -60,6 +63,8 @@ def main(argv=None):
     ap.add_argument("--no-ema", action="store_true", help="time plain and optimizer only (A/B against older trees)")
     ap.add_argument("--no-adam", action="store_true", help="leave the adamw engine out (A/B against older trees)")
     ap.add_argument("--no-clip", action="store_true", help="leave the adamw+clip engine out (A/B against older trees)")
+    ap.add_argument("--no-accum", action="store_true",
+                    help="leave the adamw+accum4 engine out (A/B against older trees)")
     a = ap.parse_args(argv)
     from distributeddataparallel_cifar10_amd.data.synthetic import synthetic_cifar
     from distributeddataparallel_cifar10_amd.runtime.engine import OptimizerConfig
@@ -85,6 +90,10 @@ def main(argv=None):
                 clip = OptimizerConfig(kind="adamw", betas=(0.9, 0.999), weight_decay=5e-2, lr_table=table,
                                        max_grad_norm=0.05)
                 engines["adamw+clip"] = _engine(dtype, a.batch, clip, data, labels, order)
+            if not a.no_accum:
+                accum = OptimizerConfig(kind="adamw", betas=(0.9, 0.999), weight_decay=5e-2, lr_table=table,
+                                        accumulate_steps=4)
+                engines["adamw+accum4"] = _engine(dtype, a.batch, accum, data, labels, order)
         for eng in engines.values():
             _timed(eng, a.batch, a.warmup)
         us = {k: [] for k in engines}
@@ -98,6 +107,9 @@ def main(argv=None):
                 norm, clipped = eng.grad_norm()
                 assert clipped > 0, (dtype, norm, clipped)
                 print(f"{dtype} adamw+clip: {clipped} of {total} steps clipped, last norm {norm:.4f}", flush=True)
+            if k == "adamw+accum4":  # one optimiser step per four micro-steps
+                assert eng.optimizer_step() == total // 4 and eng.accumulate_phase() == total % 4
+                print(f"{dtype} adamw+accum4: {eng.optimizer_step()} optimiser steps in {total} micro-steps", flush=True)
             eng.close()
         med = {k: statistics.median(v) for k, v in us.items()}
         out[dtype] = {"plain_us": round(med["plain"], 2), "optimizer_us": round(med["optimizer"], 2),
@@ -111,6 +123,9 @@ def main(argv=None):
         if "adamw+clip" in med:
             out[dtype].update(clip_us=round(med["adamw+clip"], 2),
                               clip_delta_us=round(med["adamw+clip"] - med["adamw"], 2))
+        if "adamw+accum4" in med:
+            out[dtype].update(accum_us=round(med["adamw+accum4"], 2),
+                              accum_delta_us=round(med["adamw+accum4"] - med["adamw"], 2))
         for k, v in us.items():
             print(f"{dtype} {k:13s} us/step: median {med[k]:.2f}  min {min(v):.2f}  max {max(v):.2f}  "
                   f"reps {' '.join(f'{x:.2f}' for x in v)}", flush=True)
@@ -125,6 +140,9 @@ def main(argv=None):
         if "adamw+clip" in med:
             print(f"{dtype} clipping costs {med['adamw+clip'] - med['adamw']:+.2f} us/step over adamw "
                   f"({100 * (med['adamw+clip'] / med['adamw'] - 1):+.1f} %)", flush=True)
+        if "adamw+accum4" in med:
+            print(f"{dtype} accumulation (K = 4) costs {med['adamw+accum4'] - med['adamw']:+.2f} us/micro-step over "
+                  f"adamw ({100 * (med['adamw+accum4'] / med['adamw'] - 1):+.1f} %)", flush=True)
     print(json.dumps({"bench": "opt_bench", "engine": "sliced", "batch": a.batch, "steps": a.steps, "reps": a.reps,
                       **out}), flush=True)
 

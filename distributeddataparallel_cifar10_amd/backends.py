@@ -13,6 +13,8 @@ Operations: ``run_epoch``, ``optimizer_state`` / ``load_optimizer_state``, ``ema
 ``evaluate``, ``comm_time``, ``check_comm``, ``grad_norm`` (``--clip-grad-norm``); attributes ``engine_name`` and ``fp32_mode`` for the metrics records.
 The optimiser state travels in the sidecar's own shape: ``{"momentum_buffer": {name: tensor}}`` or ``{"kind",
 "exp_avg": {...}, "exp_avg_sq": {...}}`` (the fused engine adds ``"engine"``, the step kernels' carried state).
+With ``--accumulate-steps K`` every step is a micro-step: ``micro`` is the open window's phase, ``optimizer_steps`` the
+optimiser steps of the last ``run_epoch``, and the state gains ``"accum"`` and ``"accumulate_steps"``.
 """
 from __future__ import annotations
 
@@ -71,11 +73,17 @@ class TorchOptimizerState:
 class _Backend:
     def __init__(self, model, cfg, rank: int, table):
         self.model, self.cfg, self.rank, self.table = model, cfg, rank, table
-        self.last_lr = cfg.lr  # the learning rate of the last step taken
+        self.last_lr = cfg.lr  # the learning rate of the last optimiser step taken
+        # --accumulate-steps K: every K-th micro-step is followed by an optimiser step; windows carry across epochs
+        self.accumulate_steps = int(getattr(cfg, "accumulate_steps", 1) or 1)
+        self.micro = 0            # micro-steps in the window that is open now, in [0, K)
+        self.optimizer_steps = 0  # optimiser steps taken by the last run_epoch (its micro-steps when K = 1)
 
     def _stepped(self, loss_sum: float, nsteps: int, opt_step: int) -> tuple:
-        if self.table is not None and nsteps:
-            self.last_lr = lr_at(self.table, opt_step + nsteps - 1)
+        """`nsteps` micro-steps were run from optimiser step `opt_step` on: count the optimiser steps among them."""
+        self.optimizer_steps, self.micro = divmod(self.micro + nsteps, self.accumulate_steps)
+        if self.table is not None and self.optimizer_steps:
+            self.last_lr = lr_at(self.table, opt_step + self.optimizer_steps - 1)
         return loss_sum, nsteps, self.last_lr
 
     def _fault(self) -> Fault:
@@ -93,6 +101,9 @@ class FusedBackend(_Backend):
             raise ValueError("--ema-decay is on but the fused trainer was built without it (train.engine_optimizer)")
         if cfg.clip_grad_norm is not None and eng.clip_part is None:
             raise ValueError("--clip-grad-norm is on but the fused trainer was built without it "
+                             "(train.engine_optimizer)")
+        if self.accumulate_steps > 1 and eng.accum is None:
+            raise ValueError("--accumulate-steps is on but the fused trainer was built without it "
                              "(train.engine_optimizer)")
         self.engine_name = eng.kind_name
         self.fp32_mode = ("3xbf16" if eng.kind_name == "sliced" else "fp32-mfma") if cfg.dtype == "fp32" else None
@@ -119,16 +130,20 @@ class FusedBackend(_Backend):
     def optimizer_state(self) -> dict:
         state = self.engine.optimizer_state()
         del state["step"]
+        state.pop("micro", None)  # (the window phase travels in the checkpoint's meta, like the step)
         return {**state, "engine": self.engine.step_state()}  # the step kernels' carried BN shifts (bitwise resume)
 
-    def load_optimizer_state(self, state: Optional[dict], step: int) -> None:
-        """`state` None (no sidecar): only the schedule position moves to `step`."""
+    def load_optimizer_state(self, state: Optional[dict], step: int, micro: int = 0) -> None:
+        """`state` None (no sidecar): only the schedule position moves to `step`.  `micro`: the window phase of
+        ``--accumulate-steps`` (the accumulated gradient is the sidecar's ``"accum"``)."""
         eng = self.engine
         if state is None:
             if step != eng.optimizer_step():
                 eng.load_optimizer_state({**eng.optimizer_state(), "step": step})
             return
-        eng.load_optimizer_state({**{k: v for k, v in state.items() if k != "engine"}, "step": int(step)})
+        eng.load_optimizer_state({**{k: v for k, v in state.items() if k != "engine"}, "step": int(step),
+                                  "micro": int(micro)})
+        self.micro = int(micro)
         if "engine" in state:
             eng.load_step_state(state["engine"])
 
@@ -167,6 +182,10 @@ class GenericBackend(_Backend):
             raise ValueError("--clip-grad-norm is on but the flat optimiser was built without max_grad_norm "
                              "(train.make_optimizer)")
         self._last_norm, self._clipped = 0.0, 0
+        self.accum = None  # --accumulate-steps K > 1: the window's gradient sum beside the model's gradients
+        if self.accumulate_steps > 1:
+            from .parallel.flat_ddp import GradAccumulator
+            self.accum = GradAccumulator(model, self.accumulate_steps)
         self.loss_fn = nn.CrossEntropyLoss()
         on_ops = isinstance(getattr(model, "module", None), OpsModel)
         if on_ops:
@@ -183,17 +202,20 @@ class GenericBackend(_Backend):
 
     def run_epoch(self, loader, steps: int, opt_step: int, fail_after: Optional[int] = None) -> tuple:
         """The reference's step loop over the first `steps` batches; `fail_after`: the injected failure is raised at
-        the step after that many."""
-        model, optimizer, table = self.model, self.optimizer, self.table
+        the step after that many.  With ``--accumulate-steps`` every step is a micro-step: its gradient is folded into
+        the window, and only the window's last one sets the learning rate (by optimiser step), clips, steps the
+        optimiser and updates the EMA."""
+        model, optimizer, table, accum = self.model, self.optimizer, self.table, self.accum
         autocast = self.autocast and loader.device.type == "cuda"
-        loss_sum, nsteps = 0.0, 0
+        loss_sum, nsteps, nopt = 0.0, 0, 0
         for imgs, labels in loader:
             if nsteps >= steps:
                 break
             if nsteps == fail_after:
                 raise self._fault()
-            if table is not None:  # this step's learning rate (the fused engine reads the same table on the GPU)
-                lr = lr_at(table, opt_step + nsteps)
+            last = accum is None or accum.micro == accum.steps - 1  # an optimiser step follows this backward
+            if table is not None and last:  # its learning rate (the fused engine reads the same table on the GPU)
+                lr = lr_at(table, opt_step + nopt)
                 for group in optimizer.param_groups:
                     group["lr"] = lr
             with record_function("forward"), torch.autocast("cuda", torch.bfloat16, enabled=autocast):
@@ -204,11 +226,15 @@ class GenericBackend(_Backend):
                 loss.backward(_seed_grad(loss))
             with record_function("optimizer"):
                 norm = None
-                if self.clip_torch:
-                    norm = torch.nn.utils.clip_grad_norm_(model.parameters(), self.cfg.clip_grad_norm)
-                optimizer.step()
-                if self.ema is not None:
-                    self.ema.update(opt_step + nsteps)
+                if accum is not None:
+                    accum.accumulate()
+                if last:
+                    if self.clip_torch:
+                        norm = torch.nn.utils.clip_grad_norm_(model.parameters(), self.cfg.clip_grad_norm)
+                    optimizer.step()
+                    if self.ema is not None:
+                        self.ema.update(opt_step + nopt)
+                    nopt += 1
             loss_sum += loss.item()
             if norm is not None:
                 self._last_norm = float(norm)
@@ -217,11 +243,17 @@ class GenericBackend(_Backend):
         return self._stepped(loss_sum, nsteps, opt_step)
 
     def optimizer_state(self) -> dict:
-        return self.opt_state.sidecar_state()
+        state = self.opt_state.sidecar_state()
+        if self.accum is not None:
+            state = {**state, "accum": self.accum.state(), "accumulate_steps": self.accumulate_steps}
+        return state
 
-    def load_optimizer_state(self, state: Optional[dict], step: int) -> None:
+    def load_optimizer_state(self, state: Optional[dict], step: int, micro: int = 0) -> None:
         if state is not None:
             self.opt_state.load_sidecar_state(state, step)
+            if self.accum is not None:
+                self.accum.load_state(state.get("accum", {}), micro)
+                self.micro = int(micro)
 
     def grad_norm(self) -> Optional[tuple]:
         """As ``FusedBackend.grad_norm``."""

@@ -145,6 +145,7 @@ struct Engine {
   float* lr_table = nullptr;    // device learning-rate table (owned)
   bool ema_on = false;          // the pass runs in its EMA form (dca_engine_set_ema; opt.ema is then set)
   bool clip_on = false;         // the pass runs in its CLIP form behind k_grad_sqnorm (dca_engine_set_clip)
+  bool acc_on = false;          // the pass runs in its ACC form behind k_grad_accum (dca_engine_set_accum)
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -290,14 +291,25 @@ static int enqueue_xgmi(Engine* e, const Ctx& cx, float* dst, int apply) {
 
 // The optimiser pass over the flat buffer (momentum, weight decay, the step's learning rate; derived weight copies;
 // CC4 base) -- in place of the step's own SGD when an optimiser is set.
-static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
+static int enqueue_opt_pass(Engine* e, const Ctx& cx) {
   if (e->clip_on) HIPCK(launch_grad_sqnorm(cx, e->opt.part, e->st));  // the CLIP form reads its partials
   if (e->opt.rule != dca::OPT_SGD) {
-    HIPCK(launch_apply_adam(e->bf, e->ema_on, e->opt.rule == dca::OPT_ADAMW, e->clip_on, cx, e->optdev, e->st));
+    HIPCK(launch_apply_adam(e->bf, e->ema_on, e->opt.rule == dca::OPT_ADAMW, e->clip_on, e->acc_on, cx, e->optdev,
+                            e->st));
     return 0;
   }
-  HIPCK(launch_apply_opt(e->bf, e->ema_on, e->clip_on, cx, e->optdev, e->st));
+  HIPCK(launch_apply_opt(e->bf, e->ema_on, e->clip_on, e->acc_on, cx, e->optdev, e->st));
   return 0;
+}
+// With accumulation on, k_grad_accum first folds the step's gradient into opt.acc, and the norm kernel and the pass
+// read that buffer in the gradient's place: the same kernels on a Ctx whose `grads` points at it (cx.grads keeps
+// the micro-step's own gradient).
+static int enqueue_apply_opt(Engine* e, const Ctx& cx) {
+  if (!e->acc_on) return enqueue_opt_pass(e, cx);
+  HIPCK(launch_grad_accum(cx, e->optdev, e->st));
+  Ctx ax = cx;
+  ax.grads = e->opt.acc;
+  return enqueue_opt_pass(e, ax);
 }
 
 // RCCL, multi-kernel engine: bucket B (everything behind bucket A) is all-reduced on the comm stream once the
@@ -1058,7 +1070,9 @@ int dca_engine_set_optimizer(void* h, float* momentum_buf, float mu, float wd) {
   if (!on) {  // the EMA form, the CLIP form and the Adam rule go with the pass
     e->ema_on = false;
     e->clip_on = false;
+    e->acc_on = false;
     e->opt.part = nullptr;
+    e->opt.acc = nullptr;
     e->opt.ema = nullptr;
     e->opt.rule = dca::OPT_SGD;
     e->opt.v = nullptr;
@@ -1199,6 +1213,63 @@ int dca_engine_clip_state(void* h, double* gnorm, int* n_clipped, int reset) {
   HIPCK(hipMemcpy(&n, &e->optdev->n_clipped, sizeof(unsigned), hipMemcpyDeviceToHost));
   *n_clipped = (int)(n & 0x7fffffffu);
   if (reset) HIPCK(hipMemset(&e->optdev->n_clipped, 0, sizeof(unsigned)));
+  return 0;
+}
+
+// ACC form of the optimiser pass: gradient accumulation.  Every step's summed gradient is folded into `acc_buf` by
+// k_grad_accum, and only every `k`-th step's pass updates the model, on the mean of the window (optimizer.hip).
+// `acc_buf`: flat fp32 [FLAT_ALLOC] device buffer owned by the caller (16-byte aligned; a window's first step
+// overwrites it, so it needs no clearing).  Needs the optimiser on; null turns the form off.  Switching it on or off
+// drops the captured graphs (one more launch, another form of the pass); a new `k` on a running ACC form reaches them
+// as it is (device memory).  Every call restarts the window: the phase returns to 0.  Synchronous.
+int dca_engine_set_accum(void* h, float* acc_buf, int k) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on) {
+    g_err = "set_accum: no optimiser set (dca_engine_set_optimizer first)";
+    return -1;
+  }
+  if (acc_buf && k < 1) {
+    g_err = "set_accum: the number of accumulated steps must be at least 1";
+    return -1;
+  }
+  if (acc_buf && ((uintptr_t)acc_buf % 16)) {
+    g_err = "set_accum: the accumulation buffer must be 16-byte aligned";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  const bool on = acc_buf != nullptr;
+  if (on != e->acc_on) drop_graphs(e);
+  e->acc_on = false;  // (on again below, once the device block holds the buffer)
+  e->opt.acc = acc_buf;
+  e->opt.acc_k = on ? k : 0;
+  e->opt.inv_k = on ? 1.f / (float)k : 0.f;
+  HIPCK(hipMemcpy(e->optdev, &e->opt, offsetof(dca::OptDev, step), hipMemcpyHostToDevice));
+  const int zero[2] = {0, 0};
+  static_assert(offsetof(dca::OptDev, apply) == offsetof(dca::OptDev, micro) + sizeof(int), "micro | apply: one copy");
+  HIPCK(hipMemcpy(&e->optdev->micro, zero, sizeof(zero), hipMemcpyHostToDevice));
+  e->acc_on = on;
+  return 0;
+}
+
+// The window phase of the ACC form: micro-steps already folded into the current window, in [0, k).  set = 0: *value <-
+// phase; set = 1: phase <- *value (resume in mid-window; the accumulation buffer is the caller's to restore).
+// Synchronous.
+int dca_engine_accum_phase(void* h, int set, int* value) {
+  Engine* e = (Engine*)h;
+  if (!e->opt_on || !e->acc_on || !value) {
+    g_err = "accum_phase: accumulation is not on (dca_engine_set_accum first)";
+    return -1;
+  }
+  HIPCK(hipStreamSynchronize(e->st));
+  if (set) {
+    if (*value < 0 || *value >= e->opt.acc_k) {
+      g_err = "accum_phase: the phase must lie in [0, accumulated steps)";
+      return -1;
+    }
+    HIPCK(hipMemcpy(&e->optdev->micro, value, sizeof(int), hipMemcpyHostToDevice));
+  } else {
+    HIPCK(hipMemcpy(value, &e->optdev->micro, sizeof(int), hipMemcpyDeviceToHost));
+  }
   return 0;
 }
 

@@ -635,6 +635,20 @@ int dca_ops_clip_coef(const float* g, long n, float max_norm, double* state, voi
   return 0;
 }
 
+// Gradient accumulation over the flat fp32 slices acc / g of n elements (k_grad_accum): acc = first ? g : acc + g;
+// scaled != 0: acc = g = that sum * scale.  acc and g must not overlap.
+int dca_ops_grad_accum(float* acc, float* g, long n, int first, int scaled, float scale, void* stream) {
+  REQUIRE(n >= 0 && (n == 0 || (acc && g)), "grad_accum: buffer missing");
+  REQUIRE(((uintptr_t)acc % 4) == 0 && ((uintptr_t)g % 4) == 0, "grad_accum: misaligned slice");
+  REQUIRE(n == 0 || acc + n <= g || g + n <= acc, "grad_accum: acc and g overlap");
+  if (n == 0) return 0;
+  // one float4 per thread up to 512 workgroups (two per CU), grid-stride beyond
+  hipLaunchKernelGGL(k_grad_accum, dim3(grid_for((n + 3) / 4, 256, 512)), dim3(256), 0, (hipStream_t)stream, acc, g, n,
+                     first, scaled, scale);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
 // x (fp32 if is_f32 else bf16, n elements) -> q fp8 e4m3; amax_bits: device uint, zeroed here first.
 int dca_ops_quant_fp8(const void* x, int is_f32, long n, void* q, unsigned* amax_bits, void* stream) {
   hipStream_t st = (hipStream_t)stream;

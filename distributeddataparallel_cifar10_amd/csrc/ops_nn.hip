@@ -1344,6 +1344,44 @@ __global__ void __launch_bounds__(64) k_clip_coef(const double* __restrict__ par
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Gradient accumulation over a flat fp32 slice of any start alignment and length (utils/schedule.py
+// accumulate_reference): acc = first ? g : acc + g, one fp32 addition per element; with `scaled` (a window's last
+// micro-step) the sum is then multiplied by `scale` = fp32(1 / K), rounded on its own, and the product is written to
+// both acc and g, so the update that follows reads the mean where it reads a step's gradient.  The host knows the
+// window phase on these engines: first / scaled / scale are kernel arguments.  Scalar head and tail around a float4
+// body, as k_adam (slices of differently aligned buffers: everything on the scalar path).
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float accum_elem(float a, float g, bool first, bool scaled, float scale) {
+  float s = first ? g : a + g;
+  if (scaled) s = mul_rn(s, scale);
+  return s;
+}
+__global__ void __launch_bounds__(256) k_grad_accum(float* __restrict__ acc, float* __restrict__ g, long n, int first,
+                                                    int scaled, float scale) {
+  long head = (long)((16 - ((uintptr_t)acc & 15)) & 15) / 4;  // scalar elements in front of the first 16-byte boundary
+  if (head > n || ((uintptr_t)g & 15) != ((uintptr_t)acc & 15)) head = n;
+  const long n4 = (n - head) >> 2, tail0 = head + 4 * n4;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  for (long i = gid; i < n4; i += stride) {
+    const long e = head + 4 * i;
+    f32x4 gg = *(const f32x4*)(g + e), aa = gg;
+    if (!first) aa = *(const f32x4*)(acc + e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) aa[j] = accum_elem(aa[j], gg[j], first, scaled, scale);
+    *(f32x4*)(acc + e) = aa;
+    if (scaled) *(f32x4*)(g + e) = aa;
+  }
+  const long nedge = head + (n - tail0);
+  for (long i = gid; i < nedge; i += stride) {
+    const long e = i < head ? i : tail0 + (i - head);
+    const float gv = g[e];
+    const float s = accum_elem(first ? gv : acc[e], gv, first, scaled, scale);
+    acc[e] = s;
+    if (scaled) g[e] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // fp8 e4m3 (OCP) quantisation with a per-tensor scale computed on the device:
 //   amax = max |x|  (k_amax: per-block max, then atomicMax on the float bits -- non-negative floats order as
 //   unsigned ints);  q = sat(x * 448 / amax);  the GEMM multiplies by amax / 448 (inv scale) in its epilogue.

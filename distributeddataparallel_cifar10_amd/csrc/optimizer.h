@@ -30,6 +30,10 @@ struct OptDev {
   // CLIP forms (dca_engine_set_clip): the averaged gradient is scaled to an L2 norm of at most max_norm
   float max_norm;         // > 0
   double* part;           // [OPT_PARTS] k_grad_sqnorm's partial sums of squares (device, owned by the caller), or null
+  // ACC forms (dca_engine_set_accum): k_grad_accum sums acc_k steps' gradients into `acc`; the pass applies the mean
+  float* acc;             // accumulated gradient, flat fp32 [FLAT_ALLOC] (the gradient buffer's layout), or null
+  int acc_k;              // micro-steps per optimiser step (>= 1)
+  float inv_k;            // fp32(1 / acc_k)
   // ---- everything above is set by the host (copied up to offsetof(OptDev, step)); below: device state ----
   int step;               // optimiser steps taken (device counter)
   unsigned ticket;        // workgroups that have finished reading `step` in the current launch
@@ -37,6 +41,9 @@ struct OptDev {
                           // that advances `step`; the host sets them (adam_products) whenever it sets `step`
   double gnorm;           // CLIP forms: the last launch's gradient norm, before clipping
   unsigned n_clipped;     // CLIP forms: launches whose norm exceeded max_norm (the host resets it)
+  int micro;              // ACC forms: micro-steps already summed into `acc` in the current window, in [0, acc_k)
+  int apply;              // ACC forms: k_grad_accum's word to the kernels behind it: 1 on a window's last micro-step
+  unsigned acc_ticket;    // ACC forms: workgroups of k_grad_accum that have finished reading `micro`
 };
 enum { OPT_SGD = 0, OPT_ADAM = 1, OPT_ADAMW = 2 };
 
@@ -51,10 +58,17 @@ inline double adam_product(double beta, int step) {
 // Enqueue k_apply_opt<bf, ema, clip> on `st`: one pass over the flat buffer [0, OFF_RS); ema: the form that also
 // updates od->ema (which must then be set); clip: the form that scales the gradient by the coefficient it forms from
 // od->part (launch_grad_sqnorm goes first on the same stream).  Returns the launch's hipError_t.
-hipError_t launch_apply_opt(bool bf, bool ema, bool clip, const Ctx& cx, OptDev* od, hipStream_t st);
-// The same for the Adam forms, k_apply_adam<bf, ema, decoupled, clip> (od->v set, od->rule OPT_ADAM / OPT_ADAMW).
-hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, bool clip, const Ctx& cx, OptDev* od, hipStream_t st);
+// acc: the form that does nothing but the CC4 copy unless od->apply is set (launch_grad_accum goes first on the same
+// stream, and cx.grads points at od->acc).
+hipError_t launch_apply_opt(bool bf, bool ema, bool clip, bool acc, const Ctx& cx, OptDev* od, hipStream_t st);
+// The same for the Adam forms, k_apply_adam<bf, ema, decoupled, clip, acc> (od->v set, od->rule OPT_ADAM / OPT_ADAMW).
+hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, bool clip, bool acc, const Ctx& cx, OptDev* od,
+                             hipStream_t st);
 // Enqueue k_grad_sqnorm: part[OPT_PARTS] <- the partial sums of squares of the averaged gradient in cx.grads.
 hipError_t launch_grad_sqnorm(const Ctx& cx, double* part, hipStream_t st);
+// Enqueue k_grad_accum: od->acc <- the window's running sum with cx.grads added (overwritten on the window's first
+// micro-step, scaled by od->inv_k on its last), the CC4 tail copied; od->micro advances, od->apply says whether the
+// window is complete.  cx.grads is only read.
+hipError_t launch_grad_accum(const Ctx& cx, OptDev* od, hipStream_t st);
 
 }  // namespace dca

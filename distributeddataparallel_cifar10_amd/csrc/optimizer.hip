@@ -70,13 +70,28 @@ __device__ __forceinline__ float clip_coef(OptDev* od) {
   return c < 1.f ? c : (c != c ? c : 1.f);
 }
 
-template <bool BF, bool EMA, bool CLIP>
+// Head of an ACC form: whether k_grad_accum, in front of this launch, completed a window (od->apply, read by thread 0
+// and shared through LDS).  If not, the workgroup only installs the CC4 base from the accumulated buffer's tail (the
+// latest micro-step's, cx.grads being od->acc here) and the caller returns: no sweep, no EMA, no ticket, no counter.
+__device__ __forceinline__ bool acc_window_complete(const Ctx& cx, const OptDev* od, int t, int v) {
+  __shared__ int s_apply;
+  if (t == 0) s_apply = od->apply;
+  __syncthreads();
+  if (s_apply) return true;
+  if (cx.ws > 1 && v < 64) cx.rs_base[v] = cx.grads[OFF_RS + v];
+  return false;
+}
+
+template <bool BF, bool EMA, bool CLIP, bool ACC>
 __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
   __shared__ float s_lr;
   __shared__ int s_step;
   __shared__ float s_ema;  // (EMA form only: unused, and so not allocated, in the other)
   __shared__ float s_coef; // (CLIP form only)
   const int t = threadIdx.x, v = blockIdx.x * NT + t;
+  if constexpr (ACC) {
+    if (!acc_window_complete(cx, od, t, v)) return;
+  }
   if (t == 0) {
     const int st = __hip_atomic_load(&od->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int n = od->n_table;
@@ -158,12 +173,15 @@ __global__ void __launch_bounds__(NT) k_apply_opt(Ctx cx, OptDev* od) {
 // od->b1p = beta1^step, od->b2p = beta2^step (no pow: one multiplication each) and shared as floats.  The workgroup
 // that advances `step` also stores the new products.  The pads between tensors (g = p = m = v = 0) stay exactly 0:
 // m / (0 + eps) = 0.
-template <bool BF, bool EMA, bool DECOUPLED, bool CLIP>
+template <bool BF, bool EMA, bool DECOUPLED, bool CLIP, bool ACC>
 __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
   __shared__ float s_lr, s_ss, s_c2;
   __shared__ float s_ema;  // (EMA form only)
   __shared__ float s_coef; // (CLIP form only)
   const int t = threadIdx.x, v = blockIdx.x * NT + t;
+  if constexpr (ACC) {
+    if (!acc_window_complete(cx, od, t, v)) return;
+  }
   int st0 = 0;             // thread 0: the step and the products of this launch (t = step + 1)
   double b1t = 0., b2t = 0.;
   if (t == 0) {
@@ -251,33 +269,39 @@ __global__ void __launch_bounds__(NT) k_apply_adam(Ctx cx, OptDev* od) {
 }
 
 // The launchers name the forms without CLIP first, in the order they always had, and the CLIP forms and k_grad_sqnorm
-// behind them: the compiler keeps that order in the code object, so the forms without CLIP stay where they were.
+// behind them: the compiler keeps that order in the code object, so the forms without CLIP stay where they were.  The
+// ACC forms and k_grad_accum follow behind those, at the end of the file, for the same reason.
 typedef void (*OptKernel)(Ctx, OptDev*);
 static OptKernel adam_clip_kernel(bool bf, bool ema, bool decoupled);
 static OptKernel opt_clip_kernel(bool bf, bool ema);
+static OptKernel adam_acc_kernel(bool bf, bool ema, bool decoupled, bool clip);
+static OptKernel opt_acc_kernel(bool bf, bool ema, bool clip);
 
-hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, bool clip, const Ctx& cx, OptDev* od, hipStream_t st) {
+hipError_t launch_apply_adam(bool bf, bool ema, bool decoupled, bool clip, bool acc, const Ctx& cx, OptDev* od,
+                             hipStream_t st) {
   OptKernel k = nullptr;
-#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D, false>
+#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D, false, false>
   DCA_ADAM(false, false, false); DCA_ADAM(false, false, true); DCA_ADAM(false, true, false); DCA_ADAM(false, true, true);
   DCA_ADAM(true, false, false); DCA_ADAM(true, false, true); DCA_ADAM(true, true, false); DCA_ADAM(true, true, true);
 #undef DCA_ADAM
   if (clip) k = adam_clip_kernel(bf, ema, decoupled);
+  if (acc) k = adam_acc_kernel(bf, ema, decoupled, clip);
   hipLaunchKernelGGL(k, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
   return hipGetLastError();
 }
 
-hipError_t launch_apply_opt(bool bf, bool ema, bool clip, const Ctx& cx, OptDev* od, hipStream_t st) {
-  OptKernel k = bf ? k_apply_opt<true, false, false> : k_apply_opt<false, false, false>;
-  if (ema) k = bf ? k_apply_opt<true, true, false> : k_apply_opt<false, true, false>;
+hipError_t launch_apply_opt(bool bf, bool ema, bool clip, bool acc, const Ctx& cx, OptDev* od, hipStream_t st) {
+  OptKernel k = bf ? k_apply_opt<true, false, false, false> : k_apply_opt<false, false, false, false>;
+  if (ema) k = bf ? k_apply_opt<true, true, false, false> : k_apply_opt<false, true, false, false>;
   if (clip) k = opt_clip_kernel(bf, ema);
+  if (acc) k = opt_acc_kernel(bf, ema, clip);
   hipLaunchKernelGGL(k, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
   return hipGetLastError();
 }
 
 static OptKernel adam_clip_kernel(bool bf, bool ema, bool decoupled) {
   OptKernel k = nullptr;
-#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D, true>
+#define DCA_ADAM(B, E, D) if (bf == B && ema == E && decoupled == D) k = k_apply_adam<B, E, D, true, false>
   DCA_ADAM(false, false, false); DCA_ADAM(false, false, true); DCA_ADAM(false, true, false); DCA_ADAM(false, true, true);
   DCA_ADAM(true, false, false); DCA_ADAM(true, false, true); DCA_ADAM(true, true, false); DCA_ADAM(true, true, true);
 #undef DCA_ADAM
@@ -285,8 +309,8 @@ static OptKernel adam_clip_kernel(bool bf, bool ema, bool decoupled) {
 }
 
 static OptKernel opt_clip_kernel(bool bf, bool ema) {
-  if (ema) return bf ? k_apply_opt<true, true, true> : k_apply_opt<false, true, true>;
-  return bf ? k_apply_opt<true, false, true> : k_apply_opt<false, false, true>;
+  if (ema) return bf ? k_apply_opt<true, true, true, false> : k_apply_opt<false, true, true, false>;
+  return bf ? k_apply_opt<true, false, true, false> : k_apply_opt<false, false, true, false>;
 }
 
 // The squared L2 norm of the averaged gradient x = fp32(g * inv_ws) over the parameter elements of cx.grads, as
@@ -318,6 +342,85 @@ __global__ void __launch_bounds__(NT) k_grad_sqnorm(Ctx cx, double* __restrict__
 
 hipError_t launch_grad_sqnorm(const Ctx& cx, double* part, hipStream_t st) {
   hipLaunchKernelGGL(k_grad_sqnorm<>, dim3(OPT_NB), dim3(NT), 0, st, cx, part);
+  return hipGetLastError();
+}
+
+// The ACC forms (k_apply_opt<BF, EMA, CLIP, true>, k_apply_adam<BF, EMA, DECOUPLED, CLIP, true>; dca_engine_set_accum):
+// gradient accumulation over od->acc_k micro-steps.  k_grad_accum runs in front of k_grad_sqnorm and the pass on every
+// micro-step and keeps the window's sum in od->acc, per element in fp32 and in this order:
+//   acc = g_1;  acc = acc + g_k (k = 2 .. K);  on the K-th: G = mul_rn(acc, inv_k), inv_k = fp32(1 / K)
+// -- the first micro-step of a window overwrites, so nothing of the window before (or of a poisoned buffer) survives.
+// k_grad_sqnorm and the pass are then launched with a Ctx whose `grads` is od->acc, so G takes the gradient's place in
+// everything downstream; on the other micro-steps the pass's ACC form returns after its CC4 copy (acc_window_complete).
+// The window phase od->micro and K live in device memory: a captured step graph is the same for every phase.
+static OptKernel adam_acc_kernel(bool bf, bool ema, bool decoupled, bool clip) {
+  OptKernel k = nullptr;
+#define DCA_ADAM(B, E, D)                                         \
+  if (bf == B && ema == E && decoupled == D)                      \
+  k = clip ? k_apply_adam<B, E, D, true, true> : k_apply_adam<B, E, D, false, true>
+  DCA_ADAM(false, false, false); DCA_ADAM(false, false, true); DCA_ADAM(false, true, false); DCA_ADAM(false, true, true);
+  DCA_ADAM(true, false, false); DCA_ADAM(true, false, true); DCA_ADAM(true, true, false); DCA_ADAM(true, true, true);
+#undef DCA_ADAM
+  return k;
+}
+
+static OptKernel opt_acc_kernel(bool bf, bool ema, bool clip) {
+  OptKernel k = nullptr;
+#define DCA_OPT(B, E, C) if (bf == B && ema == E && clip == C) k = k_apply_opt<B, E, C, true>
+  DCA_OPT(false, false, false); DCA_OPT(false, false, true); DCA_OPT(false, true, false); DCA_OPT(false, true, true);
+  DCA_OPT(true, false, false); DCA_OPT(true, false, true); DCA_OPT(true, true, false); DCA_OPT(true, true, true);
+#undef DCA_OPT
+  return k;
+}
+
+// One float4 per thread over [0, OFF_RS), the pass's launch shape; thread 0 of each workgroup reads the phase and K and
+// shares them through LDS.  The CC4 tail [OFF_RS, OFF_RS + 64) -- rank 0's running statistics, not a gradient -- is
+// copied on every micro-step, never summed.  cx.grads is only read.  The workgroup that takes the last ticket advances
+// the phase (every workgroup has read it: the tickets are taken after) and tells the kernels behind this one whether
+// the window is complete.  No floating-point atomics, no grid-wide wait.
+// (A template only so that the compiler emits it where it is first named, behind the kernels that were here before.)
+template <int = 0>
+__global__ void __launch_bounds__(NT) k_grad_accum(Ctx cx, OptDev* od) {
+  __shared__ int s_micro, s_k;
+  __shared__ float s_inv;
+  const int t = threadIdx.x, v = blockIdx.x * NT + t;
+  if (t == 0) {
+    s_micro = __hip_atomic_load(&od->micro, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_k = od->acc_k;
+    s_inv = od->inv_k;
+  }
+  float* acc = od->acc;
+  __syncthreads();
+  const int micro = s_micro;
+  const bool last = micro >= s_k - 1;
+  if (v < OPT_V4) {
+    const int e0 = 4 * v;
+    f32x4 a = *(const f32x4*)(cx.grads + e0);
+    if (micro > 0) {
+      const f32x4 s = *(const f32x4*)(acc + e0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = s[k] + a[k];
+    }
+    if (last) {
+      const float inv = s_inv;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = mul_rn(a[k], inv);
+    }
+    *(f32x4*)(acc + e0) = a;
+  }
+  if (v < 64) acc[OFF_RS + v] = cx.grads[OFF_RS + v];
+  if (t == 0) {
+    const unsigned prev = __hip_atomic_fetch_add(&od->acc_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == gridDim.x - 1) {
+      __hip_atomic_store(&od->acc_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&od->micro, last ? 0 : micro + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&od->apply, last ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+hipError_t launch_grad_accum(const Ctx& cx, OptDev* od, hipStream_t st) {
+  hipLaunchKernelGGL(k_grad_accum<>, dim3(OPT_NB), dim3(NT), 0, st, cx, od);
   return hipGetLastError();
 }
 

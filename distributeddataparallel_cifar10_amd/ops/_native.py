@@ -138,6 +138,21 @@ def library_path() -> str:
     return _build.lib_path("ops")
 
 
+# Entry points added after tests/test_ops_nn_refs.py fixed its registry of what `_declare` holds: each is declared here,
+# and the test file that adds it names the GPU test that runs it (tests/test_accum.py for the one below).
+LATER_ENTRY_POINTS = {
+    # acc, g, n, first, scaled, scale, stream
+    "dca_ops_grad_accum": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                           ctypes.c_void_p],
+}
+
+
+def _declare_later(lib):
+    for name, argtypes in LATER_ENTRY_POINTS.items():
+        getattr(lib, name).argtypes = argtypes
+    return lib
+
+
 def lib():
     """The loaded ops library (built first if the sources changed); raises if it cannot be loaded."""
     global _lib
@@ -150,7 +165,7 @@ def lib():
         except Exception as exc:  # toolchain missing: only acceptable if the .so already exists
             if not os.path.exists(path):
                 raise RuntimeError(f"cannot build the ops library: {exc}") from exc
-        handle = _declare(ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL))
+        handle = _declare_later(_declare(ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)))
         if handle.dca_ops_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI {handle.dca_ops_abi_version()} != {ABI_VERSION} (stale build?)")
         if handle.dca_ops_pack_desc_size() != ctypes.sizeof(PackDesc) or \

@@ -1274,6 +1274,23 @@ def clip_coef_(grad: torch.Tensor, max_norm: float, state: torch.Tensor) -> torc
 
 
 # ------------------------------------------------------------------------------------------------------------
+# Gradient accumulation over flat fp32 buffers (utils/schedule.py accumulate_reference)
+# ------------------------------------------------------------------------------------------------------------
+def grad_accum_(acc: torch.Tensor, grad: torch.Tensor, first: bool, scale: Optional[float] = None) -> None:
+    """One micro-step of a gradient-accumulation window over flat fp32 slices of any start alignment and length:
+    ``acc = grad`` if `first` (whatever `acc` held), else ``acc = acc + grad``.  With `scale` (the window's last
+    micro-step: fp32(1 / K)) the sum is then multiplied by it, rounded on its own, and the product is written to both
+    `acc` and `grad`, so the optimiser reads the window's mean where it reads a step's gradient."""
+    _dev_check(acc, grad)
+    if acc.dtype != torch.float32 or grad.dtype != torch.float32 or not acc.is_contiguous() or \
+            not grad.is_contiguous() or acc.numel() != grad.numel():
+        raise TypeError("grad_accum_: two contiguous fp32 buffers of one length")
+    N.check(N.lib().dca_ops_grad_accum(N.ptr(acc), N.ptr(grad), acc.numel(), 1 if first else 0,
+                                       0 if scale is None else 1, 0.0 if scale is None else float(scale),
+                                       N.stream(acc.device)), "grad_accum")
+
+
+# ------------------------------------------------------------------------------------------------------------
 # Adam / AdamW over flat fp32 buffers (torch.optim.Adam / AdamW, amsgrad off; utils/schedule.py adam_reference)
 # ------------------------------------------------------------------------------------------------------------
 def adam_state(device) -> torch.Tensor:

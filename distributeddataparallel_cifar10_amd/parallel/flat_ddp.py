@@ -354,6 +354,95 @@ class FlatBucketDDP(nn.Module):
             self.xgmi = None
 
 
+class GradAccumulator:
+    """Gradient accumulation over windows of ``steps`` micro-steps for the generic engines
+    (``utils/schedule.py accumulate_reference`` is the rule).  After each backward (its gradient reduced and averaged as
+    usual, into buffers zeroed before it) ``accumulate()`` folds the gradient into an accumulation buffer -- the first
+    micro-step of a window overwrites it -- and returns whether the window is complete; on that last micro-step the
+    sum is multiplied by fp32(1 / steps) and written back into the gradient, so clipping and ``optimizer.step()`` then
+    read the window's mean where they read a step's gradient.  The caller steps the optimiser only then.
+
+    Over a ``FlatBucketDDP`` it is one buffer beside ``flat_grad``; for a plain module one buffer per parameter.  On a
+    GPU contiguous fp32 gradients go through the HIP kernel (``ops/functional.py grad_accum_``); on the CPU, and for a
+    plain module's gradients of another dtype or memory format, the same two torch operations.  Not with an
+    ``overlap=True`` optimiser: a bucket cannot be updated before the window's last micro-step."""
+
+    def __init__(self, model, steps: int):
+        from ..utils.schedule import check_accumulate_steps
+        self.steps = check_accumulate_steps(steps)
+        self.model = model
+        self.ddp = model if isinstance(model, FlatBucketDDP) else None
+        self._check_overlap()
+        self.micro = 0  # micro-steps already folded into the current window, in [0, steps)
+        self._scale = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(self.steps), dtype=torch.float32))
+        if self.ddp is not None:
+            self._named = None
+            self._acc = {None: torch.zeros_like(self.ddp.flat_grad)}
+        else:
+            self._named = {name: p for name, p in unwrap(model).named_parameters() if p.requires_grad}
+            self._acc = {name: torch.zeros_like(p, memory_format=torch.preserve_format)
+                         for name, p in self._named.items()}
+
+    def _check_overlap(self) -> None:
+        if self.ddp is not None and self.ddp._fused_opt is not None:
+            raise ValueError("gradient accumulation cannot be combined with an overlap=True optimiser: a bucket cannot "
+                             "be updated before the window's last micro-step")
+
+    @staticmethod
+    def _fold(acc: torch.Tensor, grad: torch.Tensor, first: bool, scale: Optional[float]) -> None:
+        if grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and acc.is_contiguous():
+            from ..ops.functional import grad_accum_
+            grad_accum_(acc.view(-1), grad.view(-1), first, scale)
+            return
+        if first:
+            acc.copy_(grad)
+        else:
+            acc.add_(grad)
+        if scale is not None:
+            acc.mul_(scale)
+            grad.copy_(acc)
+
+    @torch.no_grad()
+    def accumulate(self) -> bool:
+        """Fold the gradient of the backward just run into the window; True on the window's last micro-step (the
+        gradient then holds the window's mean: clip and step now)."""
+        self._check_overlap()
+        first, last = self.micro == 0, self.micro == self.steps - 1
+        scale = self._scale if last else None
+        if self.ddp is not None:
+            self._fold(self._acc[None], self.ddp.flat_grad, first, scale)
+        else:
+            for name, p in self._named.items():
+                acc = self._acc[name]
+                if p.grad is None:  # no gradient this micro-step: a zero
+                    if first:
+                        acc.zero_()
+                    if last:
+                        p.grad = acc.mul_(scale).clone()
+                    continue
+                self._fold(acc, p.grad, first, scale)
+        self.micro = 0 if last else self.micro + 1
+        return last
+
+    def state(self) -> dict:
+        """``{parameter name: accumulation buffer (a view)}`` -- the optimiser sidecar's ``"accum"``."""
+        if self.ddp is not None:
+            return self.ddp.named_views(self._acc[None])
+        return dict(self._acc)
+
+    @torch.no_grad()
+    def load_state(self, accum: dict, micro: int) -> None:
+        """Restore ``state()`` output (tensors on any device) and the window phase `micro`."""
+        if not 0 <= int(micro) < self.steps:
+            raise ValueError(f"micro must lie in [0, {self.steps}), got {micro}")
+        for name, view in self.state().items():
+            if name in accum:
+                view.copy_(accum[name])
+            elif micro:
+                raise ValueError(f"accumulation state lacks {name}")
+        self.micro = int(micro)
+
+
 class _GradClip:
     """Global gradient-norm clipping of the flat gradient for ``FlatSGD`` / ``FlatAdam``
     (``torch.nn.utils.clip_grad_norm_``; ``utils/schedule.py clip_reference`` is the rule).  On a GPU the norm and the

@@ -138,7 +138,11 @@ class OptimizerConfig:
     ``betas`` and ``eps``, the pass's Adam forms; ``weight_decay`` is then an L2 term of the gradient (``adam``) or
     decoupled (``adamw``), and ``momentum`` must be 0 (``utils/schedule.py adam_reference`` is the rule).
     ``max_grad_norm``: every update first scales the averaged gradient to a global L2 norm of at most this value
-    (``torch.nn.utils.clip_grad_norm_``; ``utils/schedule.py clip_reference`` is the rule); ``None``: no clipping."""
+    (``torch.nn.utils.clip_grad_norm_``; ``utils/schedule.py clip_reference`` is the rule); ``None``: no clipping.
+    ``accumulate_steps``: K > 1 makes every step a micro-step -- its summed gradient is folded into an accumulation
+    buffer, and only every K-th is followed by an optimiser step, on the mean of the K gradients
+    (``utils/schedule.py accumulate_reference`` is the rule); ``lr_table``, the step counter, the EMA warm-up and Adam's
+    bias correction then count optimiser steps.  1: no accumulation, exactly as without the field."""
     momentum: float = 0.0
     weight_decay: float = 0.0
     lr_table: Optional[Sequence[float]] = None
@@ -148,6 +152,7 @@ class OptimizerConfig:
     betas: Sequence[float] = (0.9, 0.999)
     eps: float = 1e-8
     max_grad_norm: Optional[float] = None
+    accumulate_steps: int = 1
 
 
 OPTIMIZER_KINDS = ("sgd", "adam", "adamw")
@@ -169,6 +174,8 @@ def check_optimizer_config(opt: OptimizerConfig) -> None:
     if opt.max_grad_norm is not None:
         from ..utils.schedule import check_max_norm
         check_max_norm(opt.max_grad_norm)
+    from ..utils.schedule import check_accumulate_steps
+    check_accumulate_steps(opt.accumulate_steps)
 
 
 def optimizer_state_kind(state: dict) -> str:
@@ -285,6 +292,7 @@ class NetResDeepEngine:
         self.ema = None  # flat fp32 [FLAT_ALLOC] average (EMA on), laid out like `grads`: running stats at OFF_RS
         self.exp_avg_sq = None  # flat fp32 second moment (an Adam kind; `momentum` is then the first moment)
         self.clip_part = None  # float64 partial sums of the gradient-norm kernel (clipping on)
+        self.accum = None  # flat fp32 [FLAT_ALLOC] accumulated gradient (accumulation on), laid out like `grads`
         if cfg.optimizer is not None:
             self.set_optimizer(cfg.optimizer)
 
@@ -295,8 +303,9 @@ class NetResDeepEngine:
         if opt is None:
             native.check(self.lib.dca_engine_set_optimizer(self.h, None, 0.0, 0.0), "dca_engine_set_optimizer")
             self.cfg.optimizer = None
-            self.ema = None  # (the EMA form, clipping and the Adam rule go with the pass)
+            self.ema = None  # (the EMA form, clipping, accumulation and the Adam rule go with the pass)
             self.clip_part = None
+            self.accum = None
             return
         check_optimizer_config(opt)
         adam = opt.kind != "sgd"
@@ -322,6 +331,8 @@ class NetResDeepEngine:
             self.set_ema_decay(opt.ema_decay, opt.ema_warmup)
         if opt.max_grad_norm is not None or self.clip_part is not None:
             self.set_max_grad_norm(opt.max_grad_norm)
+        if opt.accumulate_steps != 1 or self.accum is not None:
+            self.set_accumulate_steps(opt.accumulate_steps)
 
     def set_lr_table(self, values) -> None:
         """Per-step learning rates: optimiser step k uses ``values[min(k, len - 1)]``; an empty table returns to the
@@ -343,12 +354,19 @@ class NetResDeepEngine:
     def optimizer_state(self) -> dict:
         """``{"step": int, "momentum_buffer": {parameter name: tensor}}``, or with an Adam kind ``{"step", "kind",
         "exp_avg": {...}, "exp_avg_sq": {...}}``; the tensors are views of the flat state buffers through ``LAYOUT``
-        (clone them to keep a snapshot).  Synchronises."""
+        (clone them to keep a snapshot).  With accumulation on also ``"accum"`` (the accumulated gradient, per name),
+        ``"micro"`` (the window phase) and ``"accumulate_steps"``.  Synchronises."""
         step = self.optimizer_step()
         if self.cfg.optimizer.kind != "sgd":
-            return {"step": step, "kind": self.cfg.optimizer.kind, "exp_avg": self._views(self.momentum),
-                    "exp_avg_sq": self._views(self.exp_avg_sq)}
-        return {"step": step, "momentum_buffer": self._views(self.momentum)}
+            state = {"step": step, "kind": self.cfg.optimizer.kind, "exp_avg": self._views(self.momentum),
+                     "exp_avg_sq": self._views(self.exp_avg_sq)}
+        else:
+            state = {"step": step, "momentum_buffer": self._views(self.momentum)}
+        if self.accum is not None:
+            state["accum"] = self._views(self.accum)
+            state["micro"] = self.accumulate_phase()
+            state["accumulate_steps"] = int(self.cfg.optimizer.accumulate_steps)
+        return state
 
     @staticmethod
     def _views(flat: torch.Tensor) -> dict:
@@ -365,6 +383,21 @@ class NetResDeepEngine:
                              f"{kind!r}")
         pairs = [("momentum_buffer", self.momentum)] if kind == "sgd" else \
             [("exp_avg", self.momentum), ("exp_avg_sq", self.exp_avg_sq)]
+        micro = int(state.get("micro", 0))
+        if self.accum is not None:
+            k = int(self.cfg.optimizer.accumulate_steps)
+            theirs_k = int(state.get("accumulate_steps", k))
+            if theirs_k != k:
+                raise ValueError(f"optimiser state written with accumulate_steps={theirs_k} cannot be loaded into an "
+                                 f"engine with accumulate_steps={k}")
+            if not 0 <= micro < k:
+                raise ValueError(f"micro must lie in [0, {k}), got {micro}")
+            if "accum" in state:
+                pairs.append(("accum", self.accum))
+            elif micro:
+                raise ValueError("a state in mid-window (micro > 0) must carry \"accum\"")
+        elif micro:
+            raise ValueError("optimiser state in mid-window (micro > 0) needs an engine with accumulate_steps set")
         for key, _ in pairs:
             if set(state[key]) != set(LAYOUT):
                 raise ValueError(f"{key} must cover exactly {sorted(LAYOUT)}")
@@ -374,11 +407,16 @@ class NetResDeepEngine:
         self.sync()
         with torch.no_grad():
             for key, flat in pairs:
+                if key == "accum":  # the pads between the tensors take part in the sweep: zero, as in a fresh buffer
+                    flat.zero_()
                 for name, view in self._views(flat).items():
                     view.copy_(state[key][name].detach().to(self.device, torch.float32))
         torch.cuda.synchronize(self.device)
         v = ctypes.c_int(int(state["step"]))
         native.check(self.lib.dca_engine_opt_step(self.h, 1, ctypes.byref(v)), "dca_engine_opt_step")
+        if self.accum is not None:
+            v = ctypes.c_int(micro)
+            native.check(self.lib.dca_engine_accum_phase(self.h, 1, ctypes.byref(v)), "dca_engine_accum_phase")
 
     # ---- EMA of the weights (the optimiser pass's EMA form) --------------------------------------------------
     def set_ema_decay(self, decay: Optional[float], warmup: Optional[bool] = None) -> None:
@@ -500,6 +538,42 @@ class NetResDeepEngine:
         native.check(self.lib.dca_engine_clip_state(self.h, ctypes.byref(n), ctypes.byref(c), 1 if reset else 0),
                      "dca_engine_clip_state")
         return float(n.value), int(c.value)
+
+    # ---- gradient accumulation (k_grad_accum and the optimiser pass's ACC form) --------------------------------
+    def set_accumulate_steps(self, k: int) -> None:
+        """Micro-steps per optimiser step.  On an engine that accumulates already the captured step graphs pick a new
+        K > 1 up without re-capture; on one that does not this switches accumulation on (the buffer is allocated; one
+        more kernel per step), and ``1`` switches it off and frees the buffer -- either switch drops the captured
+        graphs.  Every call restarts the window (phase 0)."""
+        from ..utils.schedule import check_accumulate_steps
+        self._need_optimizer()
+        opt = self.cfg.optimizer
+        k = check_accumulate_steps(k)
+        if k == 1:
+            if self.accum is not None:
+                native.check(self.lib.dca_engine_set_accum(self.h, None, 1), "dca_engine_set_accum")
+            self.accum, opt.accumulate_steps = None, 1
+            return
+        fresh = self.accum is None
+        if fresh:
+            self.accum = torch.zeros(FLAT_ALLOC, dtype=torch.float32, device=self.device)
+            torch.cuda.synchronize(self.device)
+        try:
+            native.check(self.lib.dca_engine_set_accum(self.h, self.accum.data_ptr(), k), "dca_engine_set_accum")
+        except RuntimeError:
+            if fresh:
+                self.accum = None
+            raise
+        opt.accumulate_steps = k
+
+    def accumulate_phase(self) -> int:
+        """Micro-steps already folded into the current window, in ``[0, K)``: 0 right after an optimiser step.  Needs
+        accumulation on.  Synchronises."""
+        if self.accum is None:
+            raise RuntimeError("no accumulation: OptimizerConfig(accumulate_steps=K) or set_accumulate_steps()")
+        v = ctypes.c_int()
+        native.check(self.lib.dca_engine_accum_phase(self.h, 0, ctypes.byref(v)), "dca_engine_accum_phase")
+        return int(v.value)
 
     # ---- carried step state ---------------------------------------------------------------------------------
     def step_state(self) -> dict:

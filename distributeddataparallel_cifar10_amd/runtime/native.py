@@ -93,6 +93,8 @@ def _declare(lib):
     lib.dca_engine_clip_parts.restype = c_int
     # handle, norm out, clipped-steps out, reset
     lib.dca_engine_clip_state.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), c_int]
+    lib.dca_engine_set_accum.argtypes = [c_void_p, c_void_p, c_int]  # handle, accumulation buffer, steps per window
+    lib.dca_engine_accum_phase.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]  # handle, set, phase in / out
     lib.dca_eval_netresdeep.argtypes = [c_void_p, c_void_p]  # DcaEvalArgs*, hipStream_t (runtime/evaluate.py)
     # csrc/augment.hip (data/augment.py): src, dst, ids, n, n_rows, seed, epoch, pad, flip, hipStream_t; no engine
     # handle, and an error string of its own

@@ -23,7 +23,10 @@ momentum / weight decay / a per-step learning-rate schedule (``optimizer_active`
 exponential moving average of the weights, ``utils/ema.py``: kept by the fused engine's optimiser pass on the device, by
 ``ModelEma`` on the other engines; evaluated beside the live model and saved as ``<checkpoint>.ema.pt``),
 ``--optimizer adam`` / ``adamw`` (the Adam forms of the fused engine's optimiser pass, ``FlatAdam`` on ``ops``, torch's
-own on ``torch`` and the CPU; ``utils/schedule.py adam_reference`` is the rule).
+own on ``torch`` and the CPU; ``utils/schedule.py adam_reference`` is the rule), ``--clip-grad-norm``, and
+``--accumulate-steps K`` (gradient accumulation: every K-th step is followed by one optimiser step on the mean of K
+gradients -- ``k_grad_accum`` and the ACC forms of the fused engine's pass, ``GradAccumulator`` on the other engines;
+``utils/schedule.py accumulate_reference`` is the rule; micro-steps and optimiser steps are counted separately).
 """
 from __future__ import annotations
 
@@ -91,6 +94,7 @@ class TrainConfig:
     adam_beta2: float = 0.999
     adam_eps: float = 1e-8
     clip_grad_norm: Optional[float] = None  # None: off; X > 0: clip the gradient's global L2 norm to X before each update
+    accumulate_steps: int = 1        # K > 1: every K-th step is followed by one optimiser step on the mean of K gradients
     extra: dict = field(default_factory=dict)
 
 
@@ -159,6 +163,11 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
                     help="before every optimiser step, scale the (averaged) gradient so that its global L2 norm is at "
                          "most X > 0, as torch.nn.utils.clip_grad_norm_; the metrics record the norm and the number of "
                          "clipped steps (default: off)")
+    ap.add_argument("--accumulate-steps", type=int, default=_D.accumulate_steps, metavar="K",
+                    help="gradient accumulation: every step is a micro-step, and every K-th is followed by one optimiser "
+                         "step on the mean of the K gradients (effective batch K x --batch-size per rank); schedules, "
+                         "--lr-warmup-steps and the EMA count optimiser steps; micro-steps left over at the end of the "
+                         "run are dropped (default 1: off)")
     ap.add_argument("--lr-schedule", default=_D.lr_schedule, choices=["constant", "step", "cosine"],
                     help="per-step learning-rate schedule over epochs x steps-per-epoch steps (default: constant --lr)")
     ap.add_argument("--lr-warmup-steps", type=int, default=_D.lr_warmup_steps,
@@ -211,6 +220,8 @@ def config_from_args(a: argparse.Namespace, data_path_default: str) -> TrainConf
         raise SystemExit("--ema-decay must lie in [0, 1)")
     if cfg.clip_grad_norm is not None and not cfg.clip_grad_norm > 0.0:
         raise SystemExit("--clip-grad-norm must be positive")
+    if isinstance(cfg.accumulate_steps, bool) or not isinstance(cfg.accumulate_steps, int) or cfg.accumulate_steps < 1:
+        raise SystemExit("--accumulate-steps must be an integer >= 1")
     if cfg.optimizer != "sgd":  # values no Adam takes
         if cfg.momentum:
             raise SystemExit(f"--momentum belongs to --optimizer sgd; --optimizer {cfg.optimizer} takes --adam-beta1 / "
@@ -229,9 +240,12 @@ def optimizer_active(cfg: TrainConfig) -> bool:
     ``--ema-decay`` alone turns it on too: the fused engine keeps the average in its optimiser pass, so it then takes
     the split step form (with a constant table if no schedule is given).  So does ``--optimizer adam`` / ``adamw``:
     the Adam rule is a form of that pass.  And so does ``--clip-grad-norm``: the norm needs the whole reduced gradient
-    before any of it is applied, which is the split form plus one more kernel in front of the pass."""
+    before any of it is applied, which is the split form plus one more kernel in front of the pass.  And so does
+    ``--accumulate-steps K`` with K > 1: the accumulation is one more stage in front of that pass (K = 1 is off in
+    every respect)."""
     return bool(cfg.momentum or cfg.weight_decay or cfg.lr_schedule is not None or cfg.lr_warmup_steps
-                or cfg.ema_decay is not None or cfg.optimizer != "sgd" or cfg.clip_grad_norm is not None)
+                or cfg.ema_decay is not None or cfg.optimizer != "sgd" or cfg.clip_grad_norm is not None
+                or cfg.accumulate_steps > 1)
 
 
 def steps_per_epoch_of(cfg: TrainConfig, n_batches: int) -> int:
@@ -239,8 +253,10 @@ def steps_per_epoch_of(cfg: TrainConfig, n_batches: int) -> int:
 
 
 def lr_table_for(cfg: TrainConfig, n_batches: int):
-    """The run's learning-rate table (one value per optimiser step, epochs x steps per epoch), or None when no
-    optimiser option is on.  The same table drives every engine."""
+    """The run's learning-rate table (one value per optimiser step: epochs x steps per epoch, with
+    ``--accumulate-steps K`` that many // K, windows being counted over the whole run), or None when no optimiser option
+    is on.  The same table drives every engine.  ``--lr-warmup-steps`` counts optimiser steps; ``--lr-step-epochs E``
+    is E x steps per epoch // K of them."""
     if not optimizer_active(cfg):
         return None
     from .utils.schedule import lr_table
@@ -248,8 +264,9 @@ def lr_table_for(cfg: TrainConfig, n_batches: int):
     kind = cfg.lr_schedule or "constant"
     if kind == "step" and not cfg.lr_step_epochs:
         raise ValueError("--lr-schedule step needs --lr-step-epochs")
-    return lr_table(kind, cfg.lr, max(cfg.epochs * spe, 1), warmup_steps=cfg.lr_warmup_steps, min_lr=cfg.lr_min,
-                    step_size=cfg.lr_step_epochs * spe if cfg.lr_step_epochs else None, gamma=cfg.lr_gamma)
+    k = cfg.accumulate_steps
+    return lr_table(kind, cfg.lr, max(cfg.epochs * spe // k, 1), warmup_steps=cfg.lr_warmup_steps, min_lr=cfg.lr_min,
+                    step_size=cfg.lr_step_epochs * spe // k if cfg.lr_step_epochs else None, gamma=cfg.lr_gamma)
 
 
 def engine_optimizer(cfg: TrainConfig, n_batches: int):
@@ -258,10 +275,12 @@ def engine_optimizer(cfg: TrainConfig, n_batches: int):
     if table is None:
         return None
     from .runtime.engine import OptimizerConfig
+    # (accumulate_steps is passed only when set: the default call stays what it was)
+    extra = dict(accumulate_steps=cfg.accumulate_steps) if cfg.accumulate_steps > 1 else {}
     return OptimizerConfig(momentum=cfg.momentum, weight_decay=cfg.weight_decay, lr_table=table,
                            ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup, kind=cfg.optimizer,
                            betas=(cfg.adam_beta1, cfg.adam_beta2), eps=cfg.adam_eps,
-                           max_grad_norm=cfg.clip_grad_norm)
+                           max_grad_norm=cfg.clip_grad_norm, **extra)
 
 
 def augment_config(cfg: TrainConfig):
@@ -318,13 +337,15 @@ def make_optimizer(model, cfg: TrainConfig, table):
     return torch.optim.SGD(model.parameters(), lr=cfg.lr, **args)
 
 
-_STATE_TENSORS = ("momentum_buffer", "exp_avg", "exp_avg_sq")  # the sidecar's {parameter name: tensor} entries
+# the sidecar's {parameter name: tensor} entries ("accum": --accumulate-steps, the open window's gradient sum)
+_STATE_TENSORS = ("momentum_buffer", "exp_avg", "exp_avg_sq", "accum")
 
 
 def save_optimizer_state(backend, path: str, rank: int, step: int) -> None:
     """Rank 0 writes ``<checkpoint>.optim.pt`` (atomically): ``{"step", "momentum_buffer": {name: CPU tensor}}``, or
     with ``--optimizer adam`` / ``adamw`` ``{"step", "kind", "exp_avg": {...}, "exp_avg_sq": {...}}``; the fused
-    engine adds ``"engine"``, its step kernels' carried state."""
+    engine adds ``"engine"``, its step kernels' carried state.  With ``--accumulate-steps K`` also ``"accum"`` (the
+    open window's accumulated gradient, by name) and ``"accumulate_steps"``."""
     if rank != 0:
         return
     state = {"step": int(step)}
@@ -333,9 +354,12 @@ def save_optimizer_state(backend, path: str, rank: int, step: int) -> None:
     save_on_rank0(state, optim_path(path))
 
 
-def load_optimizer_state(backend, path: str, step: int, kind: str = "sgd") -> bool:
+def load_optimizer_state(backend, path: str, step: int, kind: str = "sgd", accumulate_steps: int = 1,
+                         micro: int = 0) -> bool:
     """Restore ``<checkpoint>.optim.pt`` if present (momentum buffers or Adam moments; the step counter <- `step`).
-    A sidecar written by another optimiser kind than `kind` ends the run (one without ``"kind"`` is SGD's)."""
+    A sidecar written by another optimiser kind than `kind` ends the run (one without ``"kind"`` is SGD's), and so does
+    one written with another ``--accumulate-steps`` than `accumulate_steps` (one without the entry: 1).  `micro`: the
+    window phase the checkpoint was written in; the accumulated gradient is the sidecar's ``"accum"``."""
     from .runtime.engine import optimizer_state_kind
     if not os.path.exists(optim_path(path)):
         backend.load_optimizer_state(None, step)
@@ -346,7 +370,15 @@ def load_optimizer_state(backend, path: str, step: int, kind: str = "sgd") -> bo
         raise SystemExit(f"--resume: {optim_path(path)} holds the state of --optimizer {theirs}, this run uses "
                          f"--optimizer {kind}; resume with --optimizer {theirs}, or remove the file to restart the "
                          f"optimiser state")
-    backend.load_optimizer_state(state, step)
+    theirs_k = int(state.get("accumulate_steps", 1))
+    if theirs_k != accumulate_steps:
+        raise SystemExit(f"--resume: {optim_path(path)} was written with --accumulate-steps {theirs_k}, this run uses "
+                         f"--accumulate-steps {accumulate_steps}; resume with --accumulate-steps {theirs_k}, or remove "
+                         f"the file to restart the optimiser state")
+    if accumulate_steps > 1:
+        backend.load_optimizer_state(state, step, micro)
+    else:
+        backend.load_optimizer_state(state, step)
     return True
 
 
@@ -453,7 +485,8 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
     backend = step_backend(model, cfg, rank, table, optimizer, lambda m: make_optimizer(m, cfg, table))
     if table is not None:
         if cfg.resume:  # momentum buffers of the run being resumed (absent file: they start at zero)
-            load_optimizer_state(backend, cfg.resume, opt_step, cfg.optimizer)
+            load_optimizer_state(backend, cfg.resume, opt_step, cfg.optimizer, cfg.accumulate_steps,
+                                 int(cfg.extra.get("accum_micro", 0)))
         else:
             backend.load_optimizer_state(None, opt_step)  # only the schedule position
     if cfg.ema_decay is not None and cfg.resume:
@@ -479,7 +512,7 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
         loss_sum, nsteps, last_lr = backend.run_epoch(train_loader, steps_per_epoch, opt_step, fail_after)
         global_step += nsteps
         if table is not None:
-            opt_step += nsteps
+            opt_step += backend.optimizer_steps  # (the epoch's steps, unless --accumulate-steps groups them)
         dt = time.perf_counter() - t0
         backend.check_comm()  # a peer timeout (rank-divergent gradients): raise before anything is saved
         mean = loss_sum / n_batches  # reference divides by len(train_loader) (main.py:44)
@@ -499,7 +532,10 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                    # exposed wait of the reduction kernel's gradient-segment exchanges, summed per step (xGMI)
                    allreduce_us_per_step=(comm_us / comm_n) if comm_n else None,
                    engine=backend.engine_name,
-                   lr=last_lr,  # the learning rate of the epoch's last step
+                   lr=last_lr,  # the learning rate of the last optimiser step taken
+                   # --accumulate-steps: K (null when off) and the optimiser steps among this epoch's steps
+                   accumulate_steps=cfg.accumulate_steps if cfg.accumulate_steps > 1 else None,
+                   optimizer_steps=backend.optimizer_steps if table is not None else nsteps,
                    augment=_augment_record(train_loader),
                    # the decay of the epoch's last EMA update
                    ema_decay=ema_decay_at(opt_step - 1, cfg.ema_decay, cfg.ema_warmup)
@@ -514,6 +550,8 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                 meta = {"epoch": epoch, "step": global_step}
                 if table is not None:  # optimiser sidecar: momentum buffers + the schedule position
                     meta["opt_step"] = opt_step
+                    if cfg.accumulate_steps > 1:  # the window phase; the window's sum is in the sidecar
+                        meta["accum_micro"] = backend.micro
                     save_optimizer_state(backend, ckpt, rank, opt_step)
                 save_checkpoint(model, ckpt, rank, meta=meta)
                 if cfg.ema_decay is not None and rank == 0:  # the averaged model, loadable like the checkpoint itself
@@ -524,6 +562,9 @@ def train_loop(model, train_loader: DeviceLoader, rank: int, cfg: Optional[Train
                 print(eval_line_ema(epoch, ema_ev.accuracy, ema_ev.mean_loss), flush=True)
         if cfg.check_sync and epoch % cfg.check_sync == 0:
             assert_params_in_sync(unwrap(model))
+    if cfg.accumulate_steps > 1 and backend.micro:
+        print(f"--accumulate-steps {cfg.accumulate_steps}: the run ends in mid-window, the last {backend.micro} "
+              f"micro-step(s) are dropped (no optimiser step follows them)", file=sys.stderr, flush=True)
     total = time.time() - start_time
     stack.close()
     if prof is not None:
@@ -586,6 +627,8 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
             cfg.extra["start_step"] = int(meta.get("step", 0))
             if "opt_step" in meta:
                 cfg.extra["opt_step"] = int(meta["opt_step"])
+            if "accum_micro" in meta:
+                cfg.extra["accum_micro"] = int(meta["accum_micro"])
     return wrap_model(cfg, model, loader, device)
 
 

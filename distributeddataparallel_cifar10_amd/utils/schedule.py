@@ -153,6 +153,47 @@ def clip_reference(grads, max_norm: float, inv_ws: float = 1.0):
     return norm, np.float32(coef)
 
 
+def check_accumulate_steps(k) -> int:
+    """The number of micro-steps per optimiser step as an int: ValueError unless it is an integer >= 1 (a bool, a
+    float with a fraction, a NaN are not)."""
+    bad = isinstance(k, bool)
+    try:
+        v = int(k)
+        bad = bad or v != k
+    except (TypeError, ValueError, OverflowError):
+        bad = True
+    if bad or v < 1:
+        raise ValueError(f"accumulate steps must be an integer >= 1, got {k!r}")
+    return v
+
+
+def accumulate_reference(grads, K: int):
+    """Gradient accumulation over a window of `K` micro-steps -- the oracle of ``k_grad_accum`` (both the engine's and
+    the flat one) and of ``GradAccumulator``'s CPU path.  `grads`: the K summed gradients g_1 .. g_K of the window, in
+    order (arrays or tensors of one shape).  Per element in fp32:
+
+        acc = g_1;   acc = acc + g_k  (k = 2 .. K, in order);   G = acc * fp32(1 / K)   (rounded on its own)
+
+    The first micro-step overwrites, so nothing that was in the buffer before takes part.  Returns ``(G32, G64)``: the
+    exact fp32 emulation (``numpy.float32``: what the kernels hold, bit for bit) and the same mean in float64 without
+    intermediate rounding.  G32 is what ``clip_reference`` / ``sgd_reference`` / ``adam_reference`` then receive in the
+    gradient's place (``g * inv_ws`` follows as for a single step)."""
+    K = check_accumulate_steps(K)
+    grads = list(grads)
+    if len(grads) != K:
+        raise ValueError(f"a window of K={K} micro-steps needs {K} gradients, got {len(grads)}")
+    g32 = [_f64(g).astype(np.float32) if not (isinstance(g, np.ndarray) and g.dtype == np.float32) else g
+           for g in grads]
+    with np.errstate(over="ignore", invalid="ignore"):
+        acc = g32[0].copy()
+        for g in g32[1:]:
+            acc = (acc + g).astype(np.float32)
+        inv_k = np.float32(1.0) / np.float32(K)
+        G32 = (acc * inv_k).astype(np.float32)
+        G64 = sum(g.astype(np.float64) for g in g32) / float(K)
+    return G32, G64
+
+
 def _f64(x) -> np.ndarray:
     if hasattr(x, "detach"):
         x = x.detach().cpu().double().numpy()

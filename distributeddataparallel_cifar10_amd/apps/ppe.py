@@ -11,8 +11,9 @@ workflow runs on MI355X:
   ``detection_collate`` makes ``(images, bboxes[N,5] = (batch_idx, x1, y1, x2, y2), labels[N,3], paths)``.
 * ``ResNet101ROI``: the ResNet-101 trunk (``models/resnet50.py``) + ROI-align over the stride-16 features
   (bilinear ``grid_sample``, 4x4 bins) + a 3-way multi-label head.  This is the ``model(data, bboxes)`` contract
-  of ``ppe_main_ddp.py:146``.  On GPU every conv / BN / pool / fc runs on the ops layer's HIP kernels
-  (``OpsModel.begin/stem/blocks/head``); ``engine="torch"`` keeps the stock torch modules.
+  of ``ppe_main_ddp.py:146``.  On GPU every conv / BN / pool / fc and the ROI-align itself run on the ops layer's
+  HIP kernels (``OpsModel.begin/stem/blocks/head``, ``ops.roi_align``); ``engine="torch"`` keeps the stock torch
+  modules.
 * ``train`` (``:128-182``): SGD(1e-3, momentum 0.9) via ``FlatSGD``, BCE-with-logits, progress print every 100
   iterations, ``model-ep{E}.pth`` every 5 epochs (rank 0), validation loss per epoch, loss-curve PNG.
 * ``eval_model`` / ``compute_map`` / ``plot_graph`` (``:186-231``): per-class AP (area under the interpolated
@@ -46,6 +47,8 @@ IMG_SHAPE = (120, 160)  # (H, W), reference ppe_main_ddp.py:74
 TARGETS = {"rc_nc_ma": ["rc", "nc", "ma"], "ca_ea_ma": ["ca", "ea", "ma"]}
 PIX_MEAN = (0.485, 0.456, 0.406)
 PIX_STD = (0.229, 0.224, 0.225)
+# DCA_OPS_ROI=0: the ops path gathers the ROIs with torch (grid_sample) as before (A/B comparisons)
+OPS_ROI = os.environ.get("DCA_OPS_ROI", "1") != "0"
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -181,9 +184,11 @@ class ResNet101ROI(nn.Module):
 
     def _forward_ops(self, x: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
         """The same network on the ops layer's HIP kernels (implicit-GEMM MFMA convs with the BN statistics in
-        the epilogue, fused BN + ReLU + residual, pools, fc) over NHWC bf16 activations.  Only the ROI gather
-        (bilinear ``grid_sample`` of a few boxes per image) stays in torch.  Training-mode BN trains; eval mode
-        is the inference path (running statistics, under no_grad)."""
+        the epilogue, fused BN + ReLU + residual, pools, fc) over NHWC bf16 activations.  The ROI gather is
+        ``ops.roi_align``: one launch each way on the NHWC bf16 tensors, the backward a gather with a fixed
+        summation order (torch's ``grid_sample`` chain only for a feature map its launchers reject, or with
+        DCA_OPS_ROI=0).  Training-mode BN trains; eval mode is the inference path (running statistics, under
+        no_grad)."""
         ops = self.__dict__.get("_ops")
         if ops is None:  # kept out of the module tree: OpsModel wraps this module (no state_dict cycle)
             from ..ops import OpsModel
@@ -191,9 +196,13 @@ class ResNet101ROI(nn.Module):
         h = ops.begin(x)
         h = ops.stem(h, self.stem[0], self.stem[1])
         h = ops.blocks(h, [*self.layer1, *self.layer2, *self.layer3])             # stride 16, NHWC bf16
-        r = self.roi_align(h.permute(0, 3, 1, 2).float(), boxes.float(), 16.0)  # [N,1024,bins,bins] fp32
-        h = ops.blocks(r.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous(), self.layer4)
-        return ops.head(h, self.fc)
+        from ..ops import functional as opsF
+        if OPS_ROI and opsF.roi_align_ok(h, self.bins, boxes.shape[0]):
+            r = opsF.roi_align(h, boxes, self.bins, 16.0)                          # [N,bins,bins,1024] NHWC bf16
+        else:
+            r = self.roi_align(h.permute(0, 3, 1, 2).float(), boxes.float(), 16.0)  # [N,1024,bins,bins] fp32
+            r = r.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()
+        return ops.head(ops.blocks(r, self.layer4), self.fc)
 
 
 def freeze_backbone(model: nn.Module) -> None:

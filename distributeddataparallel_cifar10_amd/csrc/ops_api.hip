@@ -191,6 +191,7 @@ void bn_fin_launch(float* part, int nparts, long M, int C, float* a0, float* a1,
 
 using namespace dca::ops;
 #include "ops_gemm_route.hip"
+#include "ops_roi.hip"
 
 namespace {
 thread_local GemmRoute g_route = {};      // of this thread's last dca_ops_gemm (dca_ops_gemm_last_route)
@@ -200,7 +201,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 16; }
+int dca_ops_abi_version() { return 17; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -712,5 +713,56 @@ int dca_ops_pack_gather(const void* descs, int nd, int blocks, void* stream) {
 }
 
 int dca_ops_gather_desc_size() { return (int)sizeof(GatherDesc); }
+
+// ROI-align (ops_roi.hip).  feat / dfeat: dense NHWC bf16 [B][h][w][C]; boxes: N rows of 5 floats (batch index, x1,
+// y1, x2, y2 in input pixels); out / dout: dense bf16 [N][k][k][C] (ops/functional.py checks that the tensors are
+// contiguous).  Any box values are safe: the kernels clamp every index.  N == 0: the forward does nothing, the backward
+// writes zeros.
+static const char* roi_rule(int B, int h, int w, int C, int N, int k, float stride) {
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || N < 0) return "roi_align: bad shape";
+  if (C % 8) return "roi_align: C % 8 != 0";
+  if (k < 1 || k > ROI_KMAX) return "roi_align: bins outside 1..8";
+  if (h > ROI_HWMAX || w > ROI_HWMAX) return "roi_align: feature map larger than 64 x 64";
+  if (!(stride > 0.f)) return "roi_align: stride must be positive";
+  if ((long)B * h * w * C >= (1L << 31) || (long)N * k * k * C >= (1L << 31)) return "roi_align: 2^31 elements or more";
+  if ((C + 255) / 256 > 65535 || B > 65535) return "roi_align: more than 65535 images or 256-channel slabs (grid.y)";
+  return nullptr;
+}
+static const char* roi_check(const void* feat, const void* boxes, const void* out, int B, int h, int w, int C, int N,
+                             int k, float stride) {
+  if (const char* e = roi_rule(B, h, w, C, N, k, stride)) return e;
+  if (!feat || (N > 0 && (!boxes || !out))) return "roi_align: buffer missing";
+  if ((uintptr_t)feat % 16 || (uintptr_t)out % 16 || (uintptr_t)boxes % 4) return "roi_align: misaligned buffer";
+  return nullptr;
+}
+
+// The shape rule alone, callable with no device (ops/functional.py roi_align_ok): -1 with the error set for a shape the
+// two launchers reject
+int dca_ops_roi_align_rule(int B, int h, int w, int C, int N, int k, float stride) {
+  const char* e = roi_rule(B, h, w, C, N, k, stride);
+  REQUIRE(!e, e);
+  return 0;
+}
+
+int dca_ops_roi_align_fwd(const void* feat, const float* boxes, void* out, int B, int h, int w, int C, int N, int k,
+                          float stride, void* stream) {
+  const char* e = roi_check(feat, boxes, out, B, h, w, C, N, k, stride);
+  REQUIRE(!e, e);
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(k_roi_align_fwd, dim3(N, (C + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)feat, boxes, (bf16_t*)out, RoiGeom{B, h, w, C, N, k, stride});
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+int dca_ops_roi_align_bwd(const void* dout, const float* boxes, void* dfeat, int B, int h, int w, int C, int N, int k,
+                          float stride, void* stream) {
+  const char* e = roi_check(dfeat, boxes, dout, B, h, w, C, N, k, stride);
+  REQUIRE(!e, e);
+  hipLaunchKernelGGL(k_roi_align_bwd, dim3((C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout,
+                     boxes, (bf16_t*)dfeat, RoiGeom{B, h, w, C, N, k, stride});
+  OPCK(hipGetLastError());
+  return 0;
+}
 
 }  // extern "C"

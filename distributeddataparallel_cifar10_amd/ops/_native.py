@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 _lock = threading.Lock()
 _lib = None
 
@@ -147,8 +147,19 @@ LATER_ENTRY_POINTS = {
 }
 
 
+# ROI-align (csrc/ops_roi.hip), run on the GPU by tests/test_ops_roi_gpu.py.  A table of its own: tests/test_accum.py
+# holds LATER_ENTRY_POINTS to exactly the entry it was written for.
+ROI_ENTRY_POINTS = {
+    # feat, boxes, out, B, h, w, C, N, k, stride, stream
+    "dca_ops_roi_align_fwd": [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float, c_void_p],
+    "dca_ops_roi_align_rule": [c_int] * 6 + [c_float],  # B, h, w, C, N, k, stride
+    # dout, boxes, dfeat, B, h, w, C, N, k, stride, stream
+    "dca_ops_roi_align_bwd": [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_float, c_void_p],
+}
+
+
 def _declare_later(lib):
-    for name, argtypes in LATER_ENTRY_POINTS.items():
+    for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

@@ -1160,6 +1160,56 @@ def global_avg_pool(x, out_dtype=torch.float32):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# ROI-align (csrc/ops_roi.hip): one launch each way; the backward is a gather with a fixed summation order
+# ------------------------------------------------------------------------------------------------------------
+def roi_align_ok(feat: torch.Tensor, bins: int, n_boxes: int = 0, stride: float = 16.0) -> bool:
+    """Whether ``roi_align`` takes this feature map: a dense 16-byte-aligned NHWC bf16 tensor of a shape the launchers'
+    rule (csrc/ops_api.hip roi_rule) accepts."""
+    if not (feat.is_cuda and feat.dtype == torch.bfloat16 and feat.dim() == 4 and feat.is_contiguous()
+            and feat.data_ptr() % 16 == 0 and max(feat.shape) < 2 ** 31 and n_boxes < 2 ** 31):
+        return False
+    return N.lib().dca_ops_roi_align_rule(*feat.shape, int(n_boxes), int(bins), float(stride)) == 0
+
+
+class _RoiAlign(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, boxes, bins, stride):
+        _dev_check(feat, boxes)
+        if feat.dtype != torch.bfloat16 or feat.dim() != 4 or not feat.is_contiguous():
+            raise ValueError("roi_align: a contiguous NHWC bf16 feature map")
+        if boxes.dim() != 2 or boxes.shape[1] != 5 or boxes.device != feat.device:
+            raise ValueError("roi_align: boxes [N, 5] = (batch index, x1, y1, x2, y2) on the features' device")
+        boxes = boxes.detach().float().contiguous()
+        b, h, w, c = feat.shape
+        n = boxes.shape[0]
+        out = torch.empty(n, bins, bins, c, dtype=torch.bfloat16, device=feat.device)
+        N.check(N.lib().dca_ops_roi_align_fwd(N.ptr(feat), N.ptr(boxes), N.ptr(out), b, h, w, c, n, int(bins),
+                                              float(stride), N.stream(feat.device)), "roi_align_fwd")
+        ctx.save_for_backward(boxes)
+        ctx.geom = (b, h, w, c, n, int(bins), float(stride))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        (boxes,) = ctx.saved_tensors
+        b, h, w, c, n, bins, stride = ctx.geom
+        dout = dout.contiguous()  # bf16: autograd hands a gradient over in the output's dtype
+        dfeat = torch.empty(b, h, w, c, dtype=torch.bfloat16, device=dout.device)
+        N.check(N.lib().dca_ops_roi_align_bwd(N.ptr(dout), N.ptr(boxes), N.ptr(dfeat), b, h, w, c, n, bins, stride,
+                                              N.stream(dout.device)), "roi_align_bwd")
+        return dfeat, None, None, None
+
+
+def roi_align(feat: torch.Tensor, boxes: torch.Tensor, bins: int, stride: float) -> torch.Tensor:
+    """feat [B, h, w, C] bf16 (NHWC), boxes [N, 5] rows (batch index, x1, y1, x2, y2) in input pixels ->
+    [N, bins, bins, C] bf16: one bilinear sample per bin, align_corners = False, clamped at the border (the function
+    ``apps/ppe.py`` ``ResNet101ROI.roi_align`` defines, on the stride-`stride` feature map).  ``feat`` gets a
+    gradient, ``boxes`` does not.  Any box values are safe: the kernels clamp the batch index and every tap index."""
+    return _RoiAlign.apply(feat, boxes, bins, stride)
+
+
+# ------------------------------------------------------------------------------------------------------------
 # Cross-entropy (mean) with the softmax gradient computed in the same kernel
 # ------------------------------------------------------------------------------------------------------------
 _TICKETS = {}

@@ -192,6 +192,7 @@ void bn_fin_launch(float* part, int nparts, long M, int C, float* a0, float* a1,
 using namespace dca::ops;
 #include "ops_gemm_route.hip"
 #include "ops_roi.hip"
+#include "ops_gconv.hip"
 
 namespace {
 thread_local GemmRoute g_route = {};      // of this thread's last dca_ops_gemm (dca_ops_gemm_last_route)
@@ -201,7 +202,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 17; }
+int dca_ops_abi_version() { return 18; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -761,6 +762,111 @@ int dca_ops_roi_align_bwd(const void* dout, const float* boxes, void* dfeat, int
   REQUIRE(!e, e);
   hipLaunchKernelGGL(k_roi_align_bwd, dim3((C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout,
                      boxes, (bf16_t*)dfeat, RoiGeom{B, h, w, C, N, k, stride});
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Grouped 3 x 3 convolution (ops_gconv.hip).  x / dx: dense NHWC bf16 [N][H][W][C]; y / dy: [N][Ho][Wo][C]; w / dw: fp32
+// [C][C / groups][3][3]; the packed operands: (C / 16) * (Cg == 32 ? 9 : 5) * 1024 bytes each.
+static const char* gconv_rule(int N, int H, int W, int Cin, int Cout, int groups, int KH, int KW, int stride, int pad) {
+  static const char* rule =
+      "gconv: the grouped-convolution rule is 3x3, pad 1, stride 1 or 2, Cin == Cout == C, C % 16 == 0, "
+      "C / groups in {4, 8, 16, 32}, input rows of at most 64 pixels, fewer than 2^30 input elements (32-bit byte "
+      "offsets; the output is never larger)";
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || groups <= 1) return rule;
+  if (KH != 3 || KW != 3 || pad != 1 || (stride != 1 && stride != 2)) return rule;
+  if (Cin != Cout || Cin % 16 || Cin % groups) return rule;
+  const int cg = Cin / groups;
+  if (cg != 4 && cg != 8 && cg != 16 && cg != 32) return rule;
+  if (W > 64) return rule;
+  if ((long)N * H * W * Cin >= (1L << 30)) return rule;  // (N * strips <= 4 N < 2^31 workgroups follows)
+  return nullptr;
+}
+int dca_ops_gconv_rule(int N, int H, int W, int Cin, int Cout, int groups, int KH, int KW, int stride, int pad) {
+  const char* e = gconv_rule(N, H, W, Cin, Cout, groups, KH, KW, stride, pad);
+  REQUIRE(!e, e);
+  return 0;
+}
+static GconvGeom gconv_geom(int N, int H, int W, int C, int stride, int nparts) {
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  return GconvGeom{N, H, W, C, Ho, Wo, H, W, std::min(4, (Ho + 1) / 2), nparts};
+}
+
+int dca_ops_gconv_pack(const float* w, void* fwd, void* dgrad, int C, int groups, void* stream) {
+  const char* e = gconv_rule(1, 1, 1, C, C, groups, 3, 3, 1, 1);
+  REQUIRE(!e, e);
+  REQUIRE(w && fwd && dgrad && (uintptr_t)fwd % 16 == 0 && (uintptr_t)dgrad % 16 == 0, "gconv_pack: bad buffer");
+  const int cg = C / groups, n = 2 * (C / 16) * (cg == 32 ? 9 : 5) * 64;
+  hipLaunchKernelGGL(k_gconv_pack, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)fwd,
+                     (bf16_t*)dgrad, C, cg);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Forward.  part (or null): [nparts][C][2] fp32 BN partial sums of (y - shift[c]), every row written; nparts also
+// bounds the workgroups per 64-channel slab (>= 1).
+int dca_ops_gconv_fwd(const void* x, const void* wpk, void* y, float* part, const float* shift, int nparts, int N,
+                      int H, int W, int C, int groups, int stride, void* stream) {
+  const char* e = gconv_rule(N, H, W, C, C, groups, 3, 3, stride, 1);
+  REQUIRE(!e, e);
+  REQUIRE(x && wpk && y && nparts >= 1 && (!part || shift), "gconv_fwd: buffer missing or nparts < 1");
+  REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)wpk % 16 == 0 && (uintptr_t)y % 8 == 0, "gconv_fwd: misaligned buffer");
+  const GconvGeom g = gconv_geom(N, H, W, C, stride, nparts);
+  const dim3 grid(std::min(N * g.strips, nparts), (C + 63) / 64);
+  const bool c32 = C / groups == 32;
+#define GC_FWD(S, B)                                                                                          \
+  hipLaunchKernelGGL((k_gconv3x3_rows<S, B, false>), grid, dim3(GC_NT), 0, (hipStream_t)stream, (const bf16_t*)x, \
+                     (const bf16_t*)wpk, (bf16_t*)y, part, shift, g)
+  if (stride == 1) { if (c32) GC_FWD(1, true); else GC_FWD(1, false); }
+  else { if (c32) GC_FWD(2, true); else GC_FWD(2, false); }
+#undef GC_FWD
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Input gradient dx [N][H][W][C] from dy [N][Ho][Wo][C] and the packed dgrad operand (H, W: the forward's input).
+int dca_ops_gconv_dgrad(const void* dy, const void* wpk, void* dx, int N, int H, int W, int C, int groups, int stride,
+                        void* stream) {
+  const char* e = gconv_rule(N, H, W, C, C, groups, 3, 3, stride, 1);
+  REQUIRE(!e, e);
+  REQUIRE(dy && wpk && dx, "gconv_dgrad: buffer missing");
+  REQUIRE((uintptr_t)dy % 16 == 0 && (uintptr_t)wpk % 16 == 0 && (uintptr_t)dx % 8 == 0,
+          "gconv_dgrad: misaligned buffer");
+  GconvGeom g = gconv_geom(N, H, W, C, 1, 1);  // a stride-1 conv over the H x W grid
+  g.Hs = (H - 1) / stride + 1;
+  g.Ws = (W - 1) / stride + 1;
+  const dim3 grid(N * g.strips, (C + 63) / 64);
+  const bool c32 = C / groups == 32;
+#define GC_DG(B, D)                                                                                           \
+  hipLaunchKernelGGL((k_gconv3x3_rows<1, B, D>), grid, dim3(GC_NT), 0, (hipStream_t)stream, (const bf16_t*)dy, \
+                     (const bf16_t*)wpk, (bf16_t*)dx, (float*)nullptr, (const float*)nullptr, g)
+  if (stride == 1) { if (c32) GC_DG(true, false); else GC_DG(false, false); }
+  else { if (c32) GC_DG(true, true); else GC_DG(false, true); }
+#undef GC_DG
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Weight gradient dw [C][C / groups][3][3] fp32 (beta 1: accumulated into dw).  ws: slabs * C * 144 * (Cg == 32 ? 2 : 1)
+// floats; slabs (>= 1) bounds the workgroups per 64-channel slab.
+int dca_ops_gconv_wgrad(const void* x, const void* dy, float* ws, int slabs, float* dw, int beta, int N, int H, int W,
+                        int C, int groups, int stride, void* stream) {
+  const char* e = gconv_rule(N, H, W, C, C, groups, 3, 3, stride, 1);
+  REQUIRE(!e, e);
+  REQUIRE(x && dy && ws && dw && slabs >= 1 && (beta == 0 || beta == 1), "gconv_wgrad: buffer missing, slabs < 1 or beta");
+  REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0, "gconv_wgrad: misaligned buffer");
+  const GconvGeom g = gconv_geom(N, H, W, C, stride, slabs);
+  const int used = std::min(N * g.strips, slabs), cg = C / groups;
+  const dim3 grid(used, (C + 63) / 64);
+#define GC_WG(S, B)                                                                                        \
+  hipLaunchKernelGGL((k_gconv3x3_wgrad<S, B>), grid, dim3(GC_NT), 0, (hipStream_t)stream, (const bf16_t*)x, \
+                     (const bf16_t*)dy, ws, g)
+  if (stride == 1) { if (cg == 32) GC_WG(1, true); else GC_WG(1, false); }
+  else { if (cg == 32) GC_WG(2, true); else GC_WG(2, false); }
+#undef GC_WG
+  OPCK(hipGetLastError());
+  hipLaunchKernelGGL(k_gconv_wgrad_reduce, dim3((C * cg * 9 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)ws, dw, C, cg, used, beta);
   OPCK(hipGetLastError());
   return 0;
 }

@@ -4,7 +4,8 @@ BASELINE.json lists "ResNet-50 on synthetic 3x224x224 DDP 8xMI355X" as an extens
 framework.  The reference's second application (``ppe_main_ddp.py``) fine-tunes a ResNet-101 under the same DDP
 wrapper; its model file is missing from the reference, so the ResNet family here is defined
 from the standard architecture: stem 7x7/2 conv + 3x3/2 max-pool, stages of [3, 4, 6, 3] (ResNet-50) or
-[3, 4, 23, 3] (ResNet-101) bottlenecks with expansion 4, global average pool, fc.
+[3, 4, 23, 3] (ResNet-101) bottlenecks with expansion 4, global average pool, fc.  ``groups`` / ``width_per_group``
+give the ResNeXt members (``resnext50_32x4d``); the defaults are the plain ResNet.
 
 Training runs through the generic data-parallel path (``parallel/flat_ddp.py``: flat buffers, bucketed async
 all-reduce overlapped with backward, fused flat SGD) with bf16 autocast and channels-last activations.
@@ -20,12 +21,14 @@ import torch.nn as nn
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, in_ch: int, width: int, stride: int = 1, downsample: Optional[nn.Module] = None):
+    def __init__(self, in_ch: int, planes: int, stride: int = 1, downsample: Optional[nn.Module] = None,
+                 groups: int = 1, width_per_group: int = 64):
         super().__init__()
-        out_ch = width * self.expansion
+        out_ch = planes * self.expansion
+        width = int(planes * width_per_group / 64) * groups  # torchvision's formula (ResNeXt: wider, grouped 3x3)
         self.conv1 = nn.Conv2d(in_ch, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, bias=False)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, out_ch, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(out_ch)
@@ -41,9 +44,11 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers: List[int], num_classes: int = 1000, zero_init_residual: bool = True):
+    def __init__(self, layers: List[int], num_classes: int = 1000, zero_init_residual: bool = True,
+                 groups: int = 1, width_per_group: int = 64):
         super().__init__()
         self.in_ch = 64
+        self.groups, self.width_per_group = groups, width_per_group
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -70,9 +75,10 @@ class ResNet(nn.Module):
         down = None
         if stride != 1 or self.in_ch != out_ch:
             down = nn.Sequential(nn.Conv2d(self.in_ch, out_ch, 1, stride=stride, bias=False), nn.BatchNorm2d(out_ch))
-        mods = [Bottleneck(self.in_ch, width, stride, down)]
+        gw = dict(groups=self.groups, width_per_group=self.width_per_group)
+        mods = [Bottleneck(self.in_ch, width, stride, down, **gw)]
         self.in_ch = out_ch
-        mods += [Bottleneck(out_ch, width) for _ in range(1, blocks)]
+        mods += [Bottleneck(out_ch, width, **gw) for _ in range(1, blocks)]
         return nn.Sequential(*mods)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -87,3 +93,8 @@ def resnet50(num_classes: int = 1000) -> ResNet:
 
 def resnet101(num_classes: int = 1000) -> ResNet:
     return ResNet([3, 4, 23, 3], num_classes)
+
+
+def resnext50_32x4d(num_classes: int = 1000) -> ResNet:
+    """ResNeXt-50 32x4d: the ResNet-50 layout with 32-group 3x3 convolutions of width 128 / 256 / 512 / 1024."""
+    return ResNet([3, 4, 6, 3], num_classes, groups=32, width_per_group=4)

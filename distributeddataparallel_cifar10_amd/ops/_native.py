@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 _lock = threading.Lock()
 _lib = None
 
@@ -158,8 +158,21 @@ ROI_ENTRY_POINTS = {
 }
 
 
+# Grouped 3x3 convolution (csrc/ops_gconv.hip), run on the GPU by tests/test_ops_gconv_gpu.py.
+GCONV_ENTRY_POINTS = {
+    "dca_ops_gconv_rule": [c_int] * 10,  # N, H, W, Cin, Cout, groups, KH, KW, stride, pad
+    "dca_ops_gconv_pack": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],  # w, fwd, dgrad, C, groups, stream
+    # x, wpk, y, part, shift, nparts, N, H, W, C, groups, stride, stream
+    "dca_ops_gconv_fwd": [c_void_p] * 5 + [c_int] * 7 + [c_void_p],
+    # dy, wpk, dx, N, H, W, C, groups, stride, stream
+    "dca_ops_gconv_dgrad": [c_void_p] * 3 + [c_int] * 6 + [c_void_p],
+    # x, dy, ws, slabs, dw, beta, N, H, W, C, groups, stride, stream
+    "dca_ops_gconv_wgrad": [c_void_p] * 3 + [c_int, c_void_p] + [c_int] * 7 + [c_void_p],
+}
+
+
 def _declare_later(lib):
-    for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS}.items():
+    for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

@@ -280,10 +280,12 @@ def linear(x, w, b=None, relu=False, out_dtype=torch.float32, fp8=False):
 # ------------------------------------------------------------------------------------------------------------
 # Conv2d, NHWC: im2col (or the input itself for 1x1/stride 1) + MFMA GEMM; bias and ReLU fused in the epilogue
 # ------------------------------------------------------------------------------------------------------------
-def _geom(x, w, stride, pad):
+def _geom(x, w, stride, pad, groups=1):
     n, h, wd, c = x.shape
     co, ci, kh, kw = w.shape
-    if ci != c and not (ci < c and c % 8 == 0 and ci <= 8):  # a 3-channel stem may arrive zero-padded to 8
+    if groups > 1:
+        gconv_check(x.shape, w.shape, stride, pad, groups)
+    elif ci != c and not (ci < c and c % 8 == 0 and ci <= 8):  # a 3-channel stem may arrive zero-padded to 8
         raise ValueError(f"conv: input has {c} channels, weight expects {ci}")
     ho, wo = (h + 2 * pad - kh) // stride + 1, (wd + 2 * pad - kw) // stride + 1
     k = kh * kw * c
@@ -302,6 +304,104 @@ def _weight_matrix(w: torch.Tensor, kp: int) -> torch.Tensor:
 
 def _implicit_ok(g) -> bool:
     return g.C % 8 == 0
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Grouped 3x3 convolution (csrc/ops_gconv.hip).  The shape rule lives in the launchers (dca_ops_gconv_rule, device-free).
+# The kernels fuse neither a bias nor a ReLU: conv2d(groups > 1) refuses both (ResNeXt's grouped convs feed a BN).
+# ------------------------------------------------------------------------------------------------------------
+def _gconv_rule(xshape, wshape, stride, pad, groups) -> int:
+    n, h, wd, c = (int(v) for v in xshape)
+    co, ci, kh, kw = (int(v) for v in wshape)
+    if min(n, h, wd, c, co, ci, kh, kw) <= 0 or max(n, h, wd, c, co, kh, kw, groups) >= 2 ** 31 or ci * groups != c:
+        c = -1  # (weight and input disagree: no shape the rule takes)
+    return N.lib().dca_ops_gconv_rule(n, h, wd, c, co, int(groups), kh, kw, int(stride), int(pad))
+
+
+def gconv_ok(xshape, wshape, stride, pad, groups) -> bool:
+    """Whether the grouped-convolution kernels take NHWC input ``xshape`` with weight ``wshape`` [C, C/groups, 3, 3]."""
+    return groups > 1 and _gconv_rule(xshape, wshape, stride, pad, groups) == 0
+
+
+def gconv_check(xshape, wshape, stride, pad, groups) -> None:
+    if _gconv_rule(xshape, wshape, stride, pad, groups) != 0:
+        raise ValueError(f"conv: groups={groups} with input {tuple(xshape)}, weight {tuple(wshape)}, stride {stride}, "
+                         f"pad {pad}: {N.lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def gconv_entry(w: torch.Tensor, groups: int) -> dict:
+    """The WeightPack entry of a grouped conv: the two packed bf16 MFMA operands (k_gconv_pack's layout)."""
+    c, cg = w.shape[0], w.shape[1]
+    gconv_check((1, 1, 1, c), w.shape, 1, 1, groups)
+    nbytes = c // 16 * (9 if cg == 32 else 5) * 1024
+    return dict(groups=groups, s2d=None, classes=None, q8=None, amax=None, kp=None,
+                fwd=torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w.device),
+                dgrad=torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w.device))
+
+
+def gconv_pack(w: torch.Tensor, entry: dict) -> dict:
+    """Fill the entry's operands from the fp32 master weight [C, Cg, 3, 3]: one launch."""
+    _dev_check(w)
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        raise ValueError("gconv_pack: a contiguous fp32 weight")
+    N.check(N.lib().dca_ops_gconv_pack(N.ptr(w), N.ptr(entry["fwd"]), N.ptr(entry["dgrad"]), w.shape[0],
+                                       entry["groups"], N.stream(w.device)), "gconv_pack")
+    return entry
+
+
+def gconv_fwd(x, wshape, entry, stride, part=None, shift=None, nparts=None):
+    """y [N, Ho, Wo, C] bf16 of the grouped conv over NHWC bf16 x.  part [nparts, C, 2] fp32 (optional) receives the
+    BN partial sums of y - shift, every row written; nparts alone bounds the workgroups per 64-channel slab."""
+    gconv_check(x.shape, wshape, stride, 1, entry["groups"])
+    _dev_check(x, part, shift)
+    if x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError("gconv: a contiguous NHWC bf16 input")
+    n, h, wd, c = x.shape
+    y = torch.empty(n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c, dtype=torch.bfloat16, device=x.device)
+    if part is not None:
+        nparts = part.shape[0]
+    N.check(N.lib().dca_ops_gconv_fwd(N.ptr(x), N.ptr(entry["fwd"]), N.ptr(y), N.ptr(part), N.ptr(shift),
+                                      int(nparts or 4 * n), n, h, wd, c, entry["groups"], stride, N.stream(x.device)),
+            "gconv_fwd")
+    return y
+
+
+def _gconv_operand(t, shape, name) -> None:
+    if t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"gconv: {name} is a contiguous NHWC bf16 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def gconv_dgrad(dy, xshape, entry, stride):
+    """dx [N, H, W, C] bf16 from dy [N, Ho, Wo, C] bf16 (contiguous)."""
+    n, h, wd, c = xshape
+    gconv_check(xshape, (c, c // entry["groups"], 3, 3), stride, 1, entry["groups"])
+    _dev_check(dy)
+    _gconv_operand(dy, (n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c), "dy")
+    dx = torch.empty(n, h, wd, c, dtype=torch.bfloat16, device=dy.device)
+    N.check(N.lib().dca_ops_gconv_dgrad(N.ptr(dy), N.ptr(entry["dgrad"]), N.ptr(dx), n, h, wd, c, entry["groups"],
+                                        stride, N.stream(dy.device)), "gconv_dgrad")
+    return dx
+
+
+def gconv_wgrad(x, dy, groups, stride, out=None, slabs=None):
+    """dw [C, C/groups, 3, 3] fp32 from x [N, H, W, C] and dy [N, Ho, Wo, C] (bf16, contiguous); ``out``: accumulate
+    into this contiguous fp32 view instead.  Partial slabs are summed in a fixed order (no atomics)."""
+    n, h, wd, c = x.shape
+    cg = c // groups
+    gconv_check(x.shape, (c, cg, 3, 3), stride, 1, groups)
+    _dev_check(x, dy, out)
+    _gconv_operand(x, tuple(x.shape), "x")
+    _gconv_operand(dy, (n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c), "dy")
+    slabs = int(slabs or max(16, min(512, 2048 * 64 // c)))
+    if slabs < 1:
+        raise ValueError("gconv_wgrad: at least one slab")
+    ws = torch.empty(slabs * c * 144 * (2 if cg == 32 else 1), dtype=torch.float32, device=x.device)
+    dw = out if out is not None else torch.empty(c, cg, 3, 3, dtype=torch.float32, device=x.device)
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() != c * cg * 9:
+        raise ValueError("gconv_wgrad: the gradient goes to a contiguous fp32 [C, Cg, 3, 3]")
+    N.check(N.lib().dca_ops_gconv_wgrad(N.ptr(x), N.ptr(dy), N.ptr(ws), slabs, N.ptr(dw), int(out is not None), n, h,
+                                        wd, c, groups, stride, N.stream(x.device)), "gconv_wgrad")
+    return dw
 
 
 class WeightPack:
@@ -327,6 +427,9 @@ class WeightPack:
         j = 0
         for c in self.convs:
             co, ci, kh, kw = c.weight.shape
+            if c.groups > 1:  # grouped: its own operands and one k_gconv_pack launch per step (pack())
+                self.entries[id(c)] = gconv_entry(c.weight, c.groups)
+                continue
             ci_pad = ci if ci % 8 == 0 else (ci + 7) // 8 * 8
             kp = kh * kw * ci_pad
             e = dict(ci_pad=ci_pad, kp=kp, fwd=torch.empty(co, kp, dtype=torch.bfloat16, device=dev), dgrad=None,
@@ -390,7 +493,10 @@ class WeightPack:
 
     def pack(self) -> None:
         key = tuple(c.weight.data_ptr() for c in self.convs)
-        packed = [c for c in self.convs if self.entries[id(c)]["s2d"] is None]
+        packed = [c for c in self.convs if self.entries[id(c)]["s2d"] is None and c.groups == 1]
+        for c in self.convs:
+            if c.groups > 1:
+                gconv_pack(c.weight, self.entries[id(c)])
         if key != self._key and packed:  # parameters re-pointed (e.g. into a flat DDP buffer): rebuild descriptors
             arr = (N.PackDesc * len(packed))()
             for i, c in enumerate(packed):
@@ -607,9 +713,15 @@ def _conv_fwd(x, w, b, stride, pad, relu, fp8, col_stats=None, shift=None, fp8_s
     """Forward GEMM of a conv; returns (y [N,Ho,Wo,Cout] bf16, state for _conv_bwd).  ``packed``: this conv's
     WeightPack entry (pre-built bf16 / fp8 operands) or None (operands built here from the fp32 weight)."""
     x = x.contiguous()
-    g = _geom(x, w, stride, pad)
+    groups = packed.get("groups", 1) if packed is not None else 1
+    g = _geom(x, w, stride, pad, groups)
     co = w.shape[0]
     M = g.N * g.Ho * g.Wo
+    if groups > 1:  # grouped 3x3 (csrc/ops_gconv.hip): no bias, no ReLU, never fp8
+        if b is not None or relu:
+            raise ValueError("conv: the grouped kernels fuse no bias and no ReLU")
+        y = gconv_fwd(x, w.shape, packed, stride, part=col_stats, shift=shift)
+        return y, dict(geom=g, wshape=tuple(w.shape), x=x, cols=None, packed=packed, groups=groups)
     direct = w.shape[2] == 1 and w.shape[3] == 1 and stride == 1 and pad == 0
     st = dict(geom=g, wshape=tuple(w.shape), x=x, cols=None, packed=packed)
     if packed is not None and packed["kp"] != g.K:
@@ -669,6 +781,15 @@ def _conv_bwd(dy, st, need_x: bool, need_w: bool, sink=None, x_join: Optional[Gr
     M = g.N * g.Ho * g.Wo
     dyb = dy.to(torch.bfloat16).contiguous().view(M, co)
     dx = dw = None
+    if st.get("groups", 1) > 1:  # grouped 3x3: a gather dgrad and a slab-reduced wgrad, both deterministic
+        if x_join is not None:
+            raise ValueError("conv: a grouped conv's input gradient cannot accumulate into a shared buffer")
+        dy4 = dyb.view(g.N, g.Ho, g.Wo, co)
+        if need_x:
+            dx = gconv_dgrad(dy4, (g.N, g.H, g.W, g.C), packed, g.stride)
+        if need_w:
+            dw = gconv_wgrad(st["x"], dy4, st["groups"], g.stride, out=sink)
+        return dx, (None if sink is not None else dw)
     cols = st["cols"]
     if need_x:
         acc = x_join.buf if x_join is not None else None  # accumulate into the other consumer's gradient
@@ -743,8 +864,14 @@ def _conv_bwd(dy, st, need_x: bool, need_w: bool, sink=None, x_join: Optional[Gr
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad, relu, fp8):
-        y, st = _conv_fwd(x, w, b, stride, pad, relu, fp8)
+    def forward(ctx, x, w, b, stride, pad, relu, fp8, groups=1):
+        packed = None
+        if groups > 1:  # the rule first (it needs no device), then this call's own packed operands
+            gconv_check(x.shape, w.shape, stride, pad, groups)
+            if b is not None or relu:
+                raise ValueError("conv2d: the grouped kernels fuse no bias and no ReLU")
+            packed = gconv_pack(w.detach(), gconv_entry(w, groups))
+        y, st = _conv_fwd(x, w, b, stride, pad, relu, fp8 and groups == 1, packed=packed)
         st["w_master"] = w.detach()
         ctx.st = st
         ctx.save_for_backward(y if relu else None)
@@ -759,7 +886,7 @@ class _Conv2d(torch.autograd.Function):
             dy, db = dy_prep(dy, y if ctx.relu else None, want_db=ctx.has_b and ctx.needs_input_grad[2])
         dx, dw = _conv_bwd(dy, ctx.st, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         ctx.st = None
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
 def _bn_fwd_parts(y, r, out, part, nparts, stats, gamma, beta, running_mean, running_var, eps, momentum, relu,
@@ -792,7 +919,7 @@ class _ConvBNAct(torch.autograd.Function):
             ctx.set_materialize_grads(False)
         co = w.shape[0]
         wg, stride, pad = _s2d_args(w, stride, pad, packed)
-        g = _geom(x, wg, stride, pad)
+        g = _geom(x, wg, stride, pad, packed.get("groups", 1) if packed is not None else 1)
         M = g.N * g.Ho * g.Wo
         nparts = (M + 127) // 128
         part = torch.empty(nparts, co, 2, dtype=torch.float32, device=x.device)
@@ -924,6 +1051,11 @@ def conv_bn_act(x, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, r=None, relu
         res_mode = 2 if r is not None else 0
     if conv.bias is not None:
         raise ValueError("conv_bn_act: conv without bias")
+    if conv.groups > 1:  # grouped 3x3: bf16 only; outside a WeightPack the operands are packed here
+        fp8 = False
+        if packed is None:
+            gconv_check(x.shape, conv.weight.shape, conv.stride[0], conv.padding[0], conv.groups)
+            packed = gconv_pack(conv.weight.detach(), gconv_entry(conv.weight, conv.groups))
     _check_join(bn, relu, res_mode)
     if not bn.training:  # inference: running statistics, no autograd
         _check_inference(conv.weight)
@@ -949,9 +1081,11 @@ def conv_bn_act(x, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, r=None, relu
     return max_pool2d(out, 3, 2, 1) if pool and not fuse else out
 
 
-def conv2d(x, w, b=None, stride=1, pad=0, relu=False, fp8=False):
-    """x: [N, H, W, Cin] bf16 (NHWC); w: [Cout, Cin, KH, KW] fp32 -> [N, Ho, Wo, Cout] bf16."""
-    return _Conv2d.apply(x, w, b, stride, pad, relu, fp8)
+def conv2d(x, w, b=None, stride=1, pad=0, relu=False, fp8=False, groups=1):
+    """x: [N, H, W, Cin] bf16 (NHWC); w: [Cout, Cin / groups, KH, KW] fp32 -> [N, Ho, Wo, Cout] bf16.  groups > 1: the
+    grouped 3x3 kernels, for the shapes their rule takes (``gconv_ok``; a ValueError states it otherwise), without bias,
+    ReLU or fp8."""
+    return _Conv2d.apply(x, w, b, stride, pad, relu, fp8, groups)
 
 
 # ------------------------------------------------------------------------------------------------------------

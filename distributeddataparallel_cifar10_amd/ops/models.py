@@ -119,7 +119,7 @@ class OpsModel(nn.Module):
     def _fp8_ok(self, conv) -> bool:
         """fp8 forward GEMM for 1x1 stride-1 convolutions with K = Cin >= FP8_MIN_CIN (the fp8 K-tile is 128
         deep) and for 3x3 convolutions (K = 9 Cin, implicit GEMM over the input's fp8 copy; Cin % 16 == 0)."""
-        if not self.fp8:
+        if not self.fp8 or conv.groups > 1:  # (the grouped 3x3 kernels are bf16)
             return False
         if conv.kernel_size == (3, 3):
             return conv.in_channels % 16 == 0 and conv.in_channels >= 64

@@ -69,7 +69,7 @@ class TrainConfig:
     backend: str = "nccl"
     port: Optional[int] = None
     timeout_s: Optional[float] = None
-    model: str = "netresdeep"        # netresdeep | resnet50 (generic path)
+    model: str = "netresdeep"        # netresdeep | resnet50 | resnext50 (generic path)
     bucket_mb: float = 4.0           # FlatBucketDDP bucket cap (generic path)
     profile: Optional[str] = None    # directory for torch.profiler traces / kernel summary
     check_sync: int = 0              # >0: assert cross-rank parameter equality every N epochs (and at start)
@@ -133,7 +133,7 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--world-size", type=int, default=None, help="number of ranks (default: GPU count)")
     ap.add_argument("--port", type=int, default=_D.port)
     ap.add_argument("--timeout", type=float, default=_D.timeout_s, help="process-group timeout in seconds")
-    ap.add_argument("--model", default=_D.model, choices=["netresdeep", "resnet50"])
+    ap.add_argument("--model", default=_D.model, choices=["netresdeep", "resnet50", "resnext50"])
     ap.add_argument("--bucket-mb", type=float, default=_D.bucket_mb, help="gradient bucket cap (generic DDP path)")
     ap.add_argument("--profile", default=_D.profile, metavar="DIR", help="write torch.profiler traces to DIR")
     ap.add_argument("--check-sync", type=int, default=_D.check_sync, metavar="N",
@@ -417,14 +417,17 @@ def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False, ema=No
     return evaluate_model(model, data, labels, cfg.dtype, kernel=kernel, ema=ema)
 
 
+RESNET_MODELS = {"resnet50": "resnet50", "resnext50": "resnext50_32x4d"}  # --model -> models/resnet50.py constructor
+
+
 def eval_only(cfg: TrainConfig, device: torch.device, rank: int = 0):
     """``--eval-only``: build the model, load ``cfg.resume``, evaluate, print; no engine, no training, nothing saved."""
     from .models.netresdeep import NetResDeep
     if not cfg.resume:
         raise ValueError("--eval-only requires --resume")
-    if cfg.model == "resnet50":
-        from .models.resnet50 import resnet50
-        model = resnet50(num_classes=10).to(device)
+    if cfg.model in RESNET_MODELS:
+        from .models import resnet50 as _rn
+        model = getattr(_rn, RESNET_MODELS[cfg.model])(num_classes=10).to(device)
     else:
         model = NetResDeep().to(device)
     load_checkpoint(model, cfg.resume, strict=True, map_location=device)
@@ -609,10 +612,10 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
     """The model wrapped for data parallelism on `device`: NetResDeep on the fused engine, or any model on
     FlatBucketDDP (``--model resnet50`` trains a 10-class ResNet-50 on the CIFAR tensors, channels-last, bf16)."""
     from .models.netresdeep import NetResDeep
-    if cfg.model == "resnet50":
-        from .models.resnet50 import resnet50
+    if cfg.model in RESNET_MODELS:
+        from .models import resnet50 as _rn
         torch.manual_seed(cfg.seed)
-        model = resnet50(num_classes=10).to(device)
+        model = getattr(_rn, RESNET_MODELS[cfg.model])(num_classes=10).to(device)
         if device.type == "cuda":
             model = model.to(memory_format=torch.channels_last)
         if cfg.engine == "fused":

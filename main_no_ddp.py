@@ -64,10 +64,10 @@ if __name__ == "__main__":
     if _cfg.eval_only:  # --eval-only --resume CKPT: the checkpoint's test accuracy; no training
         eval_only(_cfg, device)
         raise SystemExit(0)
-    if _cfg.model == "resnet50":
-        from distributeddataparallel_cifar10_amd.models.resnet50 import resnet50
+    if _cfg.model in ("resnet50", "resnext50"):
+        from distributeddataparallel_cifar10_amd.models.resnet50 import resnet50, resnext50_32x4d
         torch.manual_seed(_cfg.seed)
-        model = resnet50(num_classes=10).to(device)
+        model = (resnet50 if _cfg.model == "resnet50" else resnext50_32x4d)(num_classes=10).to(device)
     else:
         model = NetResDeep().to(device)
     train_loader = prepare()

@@ -193,6 +193,7 @@ using namespace dca::ops;
 #include "ops_gemm_route.hip"
 #include "ops_roi.hip"
 #include "ops_gconv.hip"
+#include "ops_dwconv.hip"
 
 namespace {
 thread_local GemmRoute g_route = {};      // of this thread's last dca_ops_gemm (dca_ops_gemm_last_route)
@@ -202,7 +203,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 18; }
+int dca_ops_abi_version() { return 19; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -867,6 +868,141 @@ int dca_ops_gconv_wgrad(const void* x, const void* dy, float* ws, int slabs, flo
   OPCK(hipGetLastError());
   hipLaunchKernelGGL(k_gconv_wgrad_reduce, dim3((C * cg * 9 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const float*)ws, dw, C, cg, used, beta);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Depthwise 3 x 3 convolution (ops_dwconv.hip).  x / dx: dense NHWC bf16 [N][H][W][C]; y / dy: [N][Ho][Wo][C]; w / dw:
+// the fp32 master weight [C][1][3][3], read directly (rounded to bf16 in the kernels): there is no packed operand.
+static const char* dwconv_rule(int N, int H, int W, int Cin, int Cout, int groups, int KH, int KW, int stride, int pad) {
+  static const char* rule =
+      "dwconv: the depthwise-convolution rule is 3x3, pad 1, stride 1 or 2, Cin == Cout == groups == C, C % 8 == 0, "
+      "input rows of 1 to 128 pixels, fewer than 2^30 input elements (32-bit byte offsets; the output is never larger)";
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0) return rule;
+  if (KH != 3 || KW != 3 || pad != 1 || (stride != 1 && stride != 2)) return rule;
+  if (Cin != Cout || Cin != groups || Cin % 8) return rule;
+  if (W > 128) return rule;
+  if ((long)N * H * W * Cin >= (1L << 30)) return rule;  // (4 N workgroups x C / 32 slabs < 2^31 follows)
+  return nullptr;
+}
+int dca_ops_dwconv_rule(int N, int H, int W, int Cin, int Cout, int groups, int KH, int KW, int stride, int pad) {
+  const char* e = dwconv_rule(N, H, W, Cin, Cout, groups, KH, KW, stride, pad);
+  REQUIRE(!e, e);
+  return 0;
+}
+static DwGeom dwconv_geom(int N, int H, int W, int C, int stride, int nparts) {
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  return DwGeom{N, H, W, C, Ho, Wo, std::min(4, (Ho + 1) / 2), nparts};
+}
+// The work split of a W-pixel input row (ops_dwconv.hip, DwPlan): log2 of the chunks per slab and the columns per
+// thread.  The widest slab whose 256 / CH columns still cover the row (stride 2 and its dgrad: half the row), and
+// no wider than the channels there are.  wmax: the widest row a 4-chunk slab with one column per thread takes.
+static void dwconv_plan(int W, int C, int wmax, int* lc, int* nc) {
+  *nc = W > wmax ? 2 : 1;
+  *lc = 2;
+  if (W <= wmax / 2 && C >= 64) *lc = 3;
+  if (W <= wmax / 4 && C >= 128) *lc = 4;
+}
+#define DW_PLAN_SWITCH(lc, nc, M) \
+  do {                            \
+    if (lc == 4) M(4, 1);         \
+    else if (lc == 3) M(3, 1);    \
+    else if (nc == 1) M(2, 1);    \
+    else M(2, 2);                 \
+  } while (0)
+#define DW_LC_SWITCH(lc, M)    \
+  do {                         \
+    if (lc == 4) M(4, 1);      \
+    else if (lc == 3) M(3, 1); \
+    else M(2, 1);              \
+  } while (0)
+
+static void dwconv_rows_launch(const void* x, const float* w, void* y, float* part, const float* shift, const DwGeom& g,
+                               int stride, int flip, hipStream_t stream) {
+  int lc, nc;
+  dwconv_plan(g.W, g.C, stride == 1 ? 64 : 128, &lc, &nc);
+  const int nslab = (g.C + (8 << lc) - 1) / (8 << lc);
+  const dim3 grid((unsigned)std::min(g.N * g.strips, g.nparts) * nslab);
+#define DW_ROWS(S, LC, NC, ST)                                                                          \
+  hipLaunchKernelGGL((k_dwconv3x3_rows<S, LC, NC, ST>), grid, dim3(DW_NT), 0, stream, (const bf16_t*)x, w, \
+                     (bf16_t*)y, part, shift, g, flip)
+#define DW_S1T(LC, NC) DW_ROWS(1, LC, NC, true)
+#define DW_S1F(LC, NC) DW_ROWS(1, LC, NC, false)
+#define DW_S2T(LC, NC) DW_ROWS(2, LC, 1, true)
+#define DW_S2F(LC, NC) DW_ROWS(2, LC, 1, false)
+  if (stride == 1) { if (part) DW_PLAN_SWITCH(lc, nc, DW_S1T); else DW_PLAN_SWITCH(lc, nc, DW_S1F); }
+  else { if (part) DW_LC_SWITCH(lc, DW_S2T); else DW_LC_SWITCH(lc, DW_S2F); }
+#undef DW_S1T
+#undef DW_S1F
+#undef DW_S2T
+#undef DW_S2F
+#undef DW_ROWS
+}
+
+// Forward.  part (or null): [nparts][C][2] fp32 BN partial sums of (y - shift[c]), every row written; nparts also
+// bounds the workgroups per slab (>= 1).
+int dca_ops_dwconv_fwd(const void* x, const float* w, void* y, float* part, const float* shift, int nparts, int N,
+                       int H, int W, int C, int groups, int stride, void* stream) {
+  const char* e = dwconv_rule(N, H, W, C, C, groups, 3, 3, stride, 1);
+  REQUIRE(!e, e);
+  REQUIRE(x && w && y && nparts >= 1 && (!part || shift), "dwconv_fwd: buffer missing or nparts < 1");
+  REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)part % 8 == 0, "dwconv_fwd: misaligned buffer");
+  dwconv_rows_launch(x, w, y, part, shift, dwconv_geom(N, H, W, C, stride, nparts), stride, 0, (hipStream_t)stream);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Input gradient dx [N][H][W][C] from dy [N][Ho][Wo][C] and the master weight (H, W: the forward's input).
+int dca_ops_dwconv_dgrad(const void* dy, const float* w, void* dx, int N, int H, int W, int C, int groups, int stride,
+                         void* stream) {
+  const char* e = dwconv_rule(N, H, W, C, C, groups, 3, 3, stride, 1);
+  REQUIRE(!e, e);
+  REQUIRE(dy && w && dx, "dwconv_dgrad: buffer missing");
+  REQUIRE((uintptr_t)dy % 16 == 0 && (uintptr_t)dx % 16 == 0, "dwconv_dgrad: misaligned buffer");
+  if (stride == 1) {  // the forward kernel over dY, taps flipped
+    // workgroups per slab: about 2048 32-channel workgroups in all (each reads its 9 x 8 weights once), as the
+    // forward's default nparts in ops/functional.py
+    const int strips = std::min(4, (H + 1) / 2), wgs = std::min(N * strips, std::max(1, 2048 * 32 / C));
+    dwconv_rows_launch(dy, w, dx, nullptr, nullptr, dwconv_geom(N, H, W, C, 1, wgs), 1, 1, (hipStream_t)stream);
+  } else {
+    const DwGeom g = dwconv_geom(N, H, W, C, 2, 1);  // units: strips of dY rows
+    int lc, nc;
+    dwconv_plan(W, C, 128, &lc, &nc);
+    const int nslab = (C + (8 << lc) - 1) / (8 << lc);
+    const dim3 grid((unsigned)(N * g.strips) * nslab);
+#define DW_DG2(LC, NC) \
+  hipLaunchKernelGGL((k_dwconv3x3_dgrad2<LC>), grid, dim3(DW_NT), 0, (hipStream_t)stream, (const bf16_t*)dy, w, (bf16_t*)dx, g)
+    DW_LC_SWITCH(lc, DW_DG2);
+#undef DW_DG2
+  }
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Weight gradient dw [C][1][3][3] fp32 (beta 1: accumulated into dw).  ws: slabs * C * 9 floats; slabs (>= 1) bounds
+// the workgroups per channel slab.
+int dca_ops_dwconv_wgrad(const void* x, const void* dy, float* ws, int slabs, float* dw, int beta, int N, int H, int W,
+                         int C, int groups, int stride, void* stream) {
+  const char* e = dwconv_rule(N, H, W, C, C, groups, 3, 3, stride, 1);
+  REQUIRE(!e, e);
+  REQUIRE(x && dy && ws && dw && slabs >= 1 && (beta == 0 || beta == 1), "dwconv_wgrad: buffer missing, slabs < 1 or beta");
+  REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0, "dwconv_wgrad: misaligned buffer");
+  const DwGeom g = dwconv_geom(N, H, W, C, stride, slabs);
+  const int used = std::min(N * g.strips, slabs);
+  int lc, nc;
+  dwconv_plan(W, C, stride == 1 ? 64 : 128, &lc, &nc);
+  const int nslab = (C + (8 << lc) - 1) / (8 << lc);
+  const dim3 grid((unsigned)used * nslab);
+#define DW_WG1(LC, NC) \
+  hipLaunchKernelGGL((k_dwconv3x3_wgrad<1, LC, NC>), grid, dim3(DW_NT), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy, ws, g)
+#define DW_WG2(LC, NC) \
+  hipLaunchKernelGGL((k_dwconv3x3_wgrad<2, LC, 1>), grid, dim3(DW_NT), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy, ws, g)
+  if (stride == 1) DW_PLAN_SWITCH(lc, nc, DW_WG1); else DW_LC_SWITCH(lc, DW_WG2);
+#undef DW_WG1
+#undef DW_WG2
+  OPCK(hipGetLastError());
+  hipLaunchKernelGGL(k_dwconv_wgrad_reduce, dim3((C * 9 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)ws, dw, C, used, beta);
   OPCK(hipGetLastError());
   return 0;
 }

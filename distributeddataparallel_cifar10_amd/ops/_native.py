@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _lock = threading.Lock()
 _lib = None
 
@@ -171,8 +171,22 @@ GCONV_ENTRY_POINTS = {
 }
 
 
+# Depthwise 3x3 convolution (csrc/ops_dwconv.hip), run on the GPU by tests/test_ops_dwconv_gpu.py.  w: the fp32 master
+# weight [C, 1, 3, 3] (there is no packed operand).
+DWCONV_ENTRY_POINTS = {
+    "dca_ops_dwconv_rule": [c_int] * 10,  # N, H, W, Cin, Cout, groups, KH, KW, stride, pad
+    # x, w, y, part, shift, nparts, N, H, W, C, groups, stride, stream
+    "dca_ops_dwconv_fwd": [c_void_p] * 5 + [c_int] * 7 + [c_void_p],
+    # dy, w, dx, N, H, W, C, groups, stride, stream
+    "dca_ops_dwconv_dgrad": [c_void_p] * 3 + [c_int] * 6 + [c_void_p],
+    # x, dy, ws, slabs, dw, beta, N, H, W, C, groups, stride, stream
+    "dca_ops_dwconv_wgrad": [c_void_p] * 3 + [c_int, c_void_p] + [c_int] * 7 + [c_void_p],
+}
+
+
 def _declare_later(lib):
-    for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS}.items():
+    for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS,
+                           **DWCONV_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

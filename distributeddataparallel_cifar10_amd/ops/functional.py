@@ -284,7 +284,7 @@ def _geom(x, w, stride, pad, groups=1):
     n, h, wd, c = x.shape
     co, ci, kh, kw = w.shape
     if groups > 1:
-        gconv_check(x.shape, w.shape, stride, pad, groups)
+        (dwconv_check if _is_depthwise(c, w.shape, groups) else gconv_check)(x.shape, w.shape, stride, pad, groups)
     elif ci != c and not (ci < c and c % 8 == 0 and ci <= 8):  # a 3-channel stem may arrive zero-padded to 8
         raise ValueError(f"conv: input has {c} channels, weight expects {ci}")
     ho, wo = (h + 2 * pad - kh) // stride + 1, (wd + 2 * pad - kw) // stride + 1
@@ -404,6 +404,89 @@ def gconv_wgrad(x, dy, groups, stride, out=None, slabs=None):
     return dw
 
 
+# ------------------------------------------------------------------------------------------------------------
+# Depthwise 3x3 convolution (csrc/ops_dwconv.hip): groups == Cin with a weight [C, 1, KH, KW].  Its own rule
+# (dca_ops_dwconv_rule, device-free); every other groups > 1 is the grouped rule's.  The kernels read the fp32 master
+# weight directly (rounded to bf16 inside), so there is no packed operand, and they fuse neither a bias nor a ReLU.
+# ------------------------------------------------------------------------------------------------------------
+def _is_depthwise(cin, wshape, groups) -> bool:
+    return groups > 1 and int(groups) == int(cin) and int(wshape[1]) == 1
+
+
+def dwconv_check(xshape, wshape, stride, pad, groups) -> None:
+    n, h, wd, c = (int(v) for v in xshape)
+    co, ci, kh, kw = (int(v) for v in wshape)
+    if min(n, h, wd, c, co, ci, kh, kw) <= 0 or max(n, h, wd, c, co, kh, kw, groups) >= 2 ** 31 or ci != 1:
+        c = -1  # (no shape the rule takes)
+    if N.lib().dca_ops_dwconv_rule(n, h, wd, c, co, int(groups), kh, kw, int(stride), int(pad)) != 0:
+        raise ValueError(f"conv: depthwise (groups={groups}) with input {tuple(xshape)}, weight {tuple(wshape)}, "
+                         f"stride {stride}, pad {pad}: {N.lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def dwconv_entry(groups: int) -> dict:
+    """The WeightPack entry of a depthwise conv: its groups and nothing to pack."""
+    return dict(groups=groups, depthwise=True, s2d=None, classes=None, q8=None, amax=None, kp=None, fwd=None, dgrad=None)
+
+
+def _dwconv_weight(w, c) -> None:
+    if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (c, 1, 3, 3):
+        raise ValueError(f"dwconv: the weight is a contiguous fp32 {(c, 1, 3, 3)}, got {w.dtype} {tuple(w.shape)}")
+
+
+def dwconv_fwd(x, w, stride, part=None, shift=None, nparts=None):
+    """y [N, Ho, Wo, C] bf16 of the depthwise conv of NHWC bf16 x with the fp32 master weight w [C, 1, 3, 3].  part
+    [nparts, C, 2] fp32 (optional) receives the BN partial sums of y - shift, every row written; nparts alone bounds
+    the workgroups per channel slab."""
+    n, h, wd, c = x.shape
+    dwconv_check(x.shape, w.shape, stride, 1, c)
+    _dev_check(x, w, part, shift)
+    _gconv_operand(x, tuple(x.shape), "x")
+    _dwconv_weight(w, c)
+    if part is not None and (part.dtype != torch.float32 or not part.is_contiguous() or part.shape[1:] != (c, 2)
+                             or shift is None or shift.dtype != torch.float32 or shift.numel() != c):
+        raise ValueError("dwconv: part is a contiguous fp32 [nparts, C, 2] and comes with an fp32 shift [C]")
+    y = torch.empty(n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c, dtype=torch.bfloat16, device=x.device)
+    if part is not None:
+        nparts = part.shape[0]
+    N.check(N.lib().dca_ops_dwconv_fwd(N.ptr(x), N.ptr(w), N.ptr(y), N.ptr(part), N.ptr(shift),
+                                       int(nparts or max(1, min(4 * n, 2048 * 32 // c))), n, h, wd, c, c, stride,
+                                       N.stream(x.device)), "dwconv_fwd")
+    return y
+
+
+def dwconv_dgrad(dy, xshape, w, stride):
+    """dx [N, H, W, C] bf16 from dy [N, Ho, Wo, C] bf16 (contiguous) and the fp32 master weight."""
+    n, h, wd, c = xshape
+    dwconv_check(xshape, w.shape, stride, 1, c)
+    _dev_check(dy, w)
+    _gconv_operand(dy, (n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c), "dy")
+    _dwconv_weight(w, c)
+    dx = torch.empty(n, h, wd, c, dtype=torch.bfloat16, device=dy.device)
+    N.check(N.lib().dca_ops_dwconv_dgrad(N.ptr(dy), N.ptr(w), N.ptr(dx), n, h, wd, c, c, stride, N.stream(dy.device)),
+            "dwconv_dgrad")
+    return dx
+
+
+def dwconv_wgrad(x, dy, stride, out=None, slabs=None):
+    """dw [C, 1, 3, 3] fp32 from x [N, H, W, C] and dy [N, Ho, Wo, C] (bf16, contiguous); ``out``: accumulate into this
+    contiguous fp32 view instead.  Partial slabs are summed in a fixed order (no atomics)."""
+    n, h, wd, c = x.shape
+    dwconv_check(x.shape, (c, 1, 3, 3), stride, 1, c)
+    _dev_check(x, dy, out)
+    _gconv_operand(x, tuple(x.shape), "x")
+    _gconv_operand(dy, (n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c), "dy")
+    slabs = int(slabs or max(16, min(512, 2048 * 32 // c)))
+    if slabs < 1:
+        raise ValueError("dwconv_wgrad: at least one slab")
+    ws = torch.empty(slabs * c * 9, dtype=torch.float32, device=x.device)
+    dw = out if out is not None else torch.empty(c, 1, 3, 3, dtype=torch.float32, device=x.device)
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() != c * 9:
+        raise ValueError("dwconv_wgrad: the gradient goes to a contiguous fp32 [C, 1, 3, 3]")
+    N.check(N.lib().dca_ops_dwconv_wgrad(N.ptr(x), N.ptr(dy), N.ptr(ws), slabs, N.ptr(dw), int(out is not None), n, h,
+                                         wd, c, c, stride, N.stream(x.device)), "dwconv_wgrad")
+    return dw
+
+
 class WeightPack:
     """The bf16 (and fp8) GEMM operands of every convolution of a model, rebuilt from the fp32 master weights
     by ONE kernel launch per step (``pack()``; csrc/ops_nn.hip k_pack_weights / k_pack_fp8) instead of a
@@ -427,6 +510,9 @@ class WeightPack:
         j = 0
         for c in self.convs:
             co, ci, kh, kw = c.weight.shape
+            if _is_depthwise(c.in_channels, c.weight.shape, c.groups):  # reads the master weight: nothing to pack
+                self.entries[id(c)] = dwconv_entry(c.groups)
+                continue
             if c.groups > 1:  # grouped: its own operands and one k_gconv_pack launch per step (pack())
                 self.entries[id(c)] = gconv_entry(c.weight, c.groups)
                 continue
@@ -495,7 +581,7 @@ class WeightPack:
         key = tuple(c.weight.data_ptr() for c in self.convs)
         packed = [c for c in self.convs if self.entries[id(c)]["s2d"] is None and c.groups == 1]
         for c in self.convs:
-            if c.groups > 1:
+            if c.groups > 1 and not self.entries[id(c)].get("depthwise"):
                 gconv_pack(c.weight, self.entries[id(c)])
         if key != self._key and packed:  # parameters re-pointed (e.g. into a flat DDP buffer): rebuild descriptors
             arr = (N.PackDesc * len(packed))()
@@ -720,6 +806,10 @@ def _conv_fwd(x, w, b, stride, pad, relu, fp8, col_stats=None, shift=None, fp8_s
     if groups > 1:  # grouped 3x3 (csrc/ops_gconv.hip): no bias, no ReLU, never fp8
         if b is not None or relu:
             raise ValueError("conv: the grouped kernels fuse no bias and no ReLU")
+        if packed.get("depthwise"):  # (csrc/ops_dwconv.hip: the master weight itself is the operand)
+            wm = w.detach()
+            y = dwconv_fwd(x, wm, stride, part=col_stats, shift=shift)
+            return y, dict(geom=g, wshape=tuple(w.shape), x=x, cols=None, packed=packed, groups=groups, dw_weight=wm)
         y = gconv_fwd(x, w.shape, packed, stride, part=col_stats, shift=shift)
         return y, dict(geom=g, wshape=tuple(w.shape), x=x, cols=None, packed=packed, groups=groups)
     direct = w.shape[2] == 1 and w.shape[3] == 1 and stride == 1 and pad == 0
@@ -785,6 +875,12 @@ def _conv_bwd(dy, st, need_x: bool, need_w: bool, sink=None, x_join: Optional[Gr
         if x_join is not None:
             raise ValueError("conv: a grouped conv's input gradient cannot accumulate into a shared buffer")
         dy4 = dyb.view(g.N, g.Ho, g.Wo, co)
+        if "dw_weight" in st:  # depthwise
+            if need_x:
+                dx = dwconv_dgrad(dy4, (g.N, g.H, g.W, g.C), st["dw_weight"], g.stride)
+            if need_w:
+                dw = dwconv_wgrad(st["x"], dy4, g.stride, out=sink)
+            return dx, (None if sink is not None else dw)
         if need_x:
             dx = gconv_dgrad(dy4, (g.N, g.H, g.W, g.C), packed, g.stride)
         if need_w:
@@ -866,7 +962,12 @@ class _Conv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, pad, relu, fp8, groups=1):
         packed = None
-        if groups > 1:  # the rule first (it needs no device), then this call's own packed operands
+        if _is_depthwise(x.shape[-1], w.shape, groups):  # the depthwise rule (device-free); nothing to pack
+            dwconv_check(x.shape, w.shape, stride, pad, groups)
+            if b is not None or relu:
+                raise ValueError("conv2d: the depthwise kernels fuse no bias and no ReLU")
+            packed = dwconv_entry(groups)
+        elif groups > 1:  # the rule first (it needs no device), then this call's own packed operands
             gconv_check(x.shape, w.shape, stride, pad, groups)
             if b is not None or relu:
                 raise ValueError("conv2d: the grouped kernels fuse no bias and no ReLU")
@@ -1053,7 +1154,10 @@ def conv_bn_act(x, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, r=None, relu
         raise ValueError("conv_bn_act: conv without bias")
     if conv.groups > 1:  # grouped 3x3: bf16 only; outside a WeightPack the operands are packed here
         fp8 = False
-        if packed is None:
+        if packed is None and _is_depthwise(x.shape[-1], conv.weight.shape, conv.groups):
+            dwconv_check(x.shape, conv.weight.shape, conv.stride[0], conv.padding[0], conv.groups)
+            packed = dwconv_entry(conv.groups)
+        elif packed is None:
             gconv_check(x.shape, conv.weight.shape, conv.stride[0], conv.padding[0], conv.groups)
             packed = gconv_pack(conv.weight.detach(), gconv_entry(conv.weight, conv.groups))
     _check_join(bn, relu, res_mode)
@@ -1083,7 +1187,8 @@ def conv_bn_act(x, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, r=None, relu
 
 def conv2d(x, w, b=None, stride=1, pad=0, relu=False, fp8=False, groups=1):
     """x: [N, H, W, Cin] bf16 (NHWC); w: [Cout, Cin / groups, KH, KW] fp32 -> [N, Ho, Wo, Cout] bf16.  groups > 1: the
-    grouped 3x3 kernels, for the shapes their rule takes (``gconv_ok``; a ValueError states it otherwise), without bias,
+    grouped 3x3 kernels (groups == Cin with a [C, 1, 3, 3] weight: the depthwise ones), for the shapes their rule takes
+    (``gconv_ok`` / ``dca_ops_dwconv_rule``; a ValueError states the rule otherwise), without bias,
     ReLU or fp8."""
     return _Conv2d.apply(x, w, b, stride, pad, relu, fp8, groups)
 

@@ -1,7 +1,7 @@
 """Model forwards on the ops layer (HIP kernels for every layer), sharing the parameters of the torch modules.
 
-``OpsModel(model)`` wraps a ``NetResDeep`` (reference ``model/resnet.py``) or a ResNet (``models/resnet50.py``)
-without copying anything: the wrapped module's ``nn.Parameter``s and BN buffers are the ones the kernels read
+``OpsModel(model)`` wraps a ``NetResDeep`` (reference ``model/resnet.py``), a ResNet (``models/resnet50.py``) or a
+MobileNetV1 (``models/mobilenet.py``) without copying anything: the wrapped module's ``nn.Parameter``s and BN buffers are the ones the kernels read
 and the optimizer updates, so ``state_dict()`` is unchanged.  The forward takes the usual NCHW fp32 batch,
 switches to channels-last bf16 once, and runs:
 
@@ -19,6 +19,9 @@ switches to channels-last bf16 once, and runs:
   weights are quantised per step (WeightPack, device-side amax); activations are emitted in
   fp8 directly by the producing BN kernel with delayed scaling (previous step's amax, ``functional.Fp8Delayed``);
   gradients and the backward stay bf16 (BASELINE config 5).
+* MobileNetV1: the ResNet entry (``begin``: 8-channel NHWC input, one pack launch), then the 3x3/2 stem (dense implicit
+  GEMM) and 13 x [depthwise 3x3 (csrc/ops_dwconv.hip) -> BN + ReLU -> 1x1 -> BN + ReLU], every conv with its BN
+  statistics from the conv kernel, -> global average pool -> fc.
 """
 from __future__ import annotations
 
@@ -38,12 +41,17 @@ def _is_netresdeep(m: nn.Module) -> bool:
     return hasattr(m, "resblocks") and hasattr(m, "fc1") and hasattr(m, "fc2")
 
 
+def _is_mobilenet(m: nn.Module) -> bool:
+    return (hasattr(m, "stem") and hasattr(m, "blocks") and hasattr(m, "fc") and len(m.blocks) > 0
+            and all(hasattr(b, "dw") and hasattr(b, "pw") for b in m.blocks))
+
+
 class OpsModel(nn.Module):
     def __init__(self, model: nn.Module, fp8: bool = False):
         super().__init__()
         self.module = model
         self.fp8 = fp8
-        self.kind = "netresdeep" if _is_netresdeep(model) else "resnet"
+        self.kind = "netresdeep" if _is_netresdeep(model) else ("mobilenet" if _is_mobilenet(model) else "resnet")
         self._pack = None
         self._s2d = None
 
@@ -51,6 +59,8 @@ class OpsModel(nn.Module):
         if self.kind == "netresdeep":
             h = x.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()  # NCHW fp32 -> NHWC bf16
             return self._netresdeep(h)
+        if self.kind == "mobilenet":
+            return self._mobilenet(self.begin(x))
         return self._resnet(self.begin(x))
 
     def begin(self, x: torch.Tensor) -> torch.Tensor:
@@ -183,4 +193,12 @@ class OpsModel(nn.Module):
         m = self.module
         h = self.stem(h, m.conv1, m.bn1)
         h = self.blocks(h, [b for stage in (m.layer1, m.layer2, m.layer3, m.layer4) for b in stage])
+        return self.head(h, m.fc)
+
+    def _mobilenet(self, h):
+        m = self.module
+        h = self._conv_bn(h, m.stem[0], m.stem[1])
+        for b in m.blocks:  # depthwise 3x3 -> BN + ReLU -> 1x1 -> BN + ReLU
+            h = self._conv_bn(h, b.dw, b.bn1, consumer=b.pw)
+            h = self._conv_bn(h, b.pw, b.bn2)
         return self.head(h, m.fc)

@@ -69,7 +69,7 @@ class TrainConfig:
     backend: str = "nccl"
     port: Optional[int] = None
     timeout_s: Optional[float] = None
-    model: str = "netresdeep"        # netresdeep | resnet50 | resnext50 (generic path)
+    model: str = "netresdeep"        # netresdeep | resnet50 | resnext50 | mobilenet (generic path)
     bucket_mb: float = 4.0           # FlatBucketDDP bucket cap (generic path)
     profile: Optional[str] = None    # directory for torch.profiler traces / kernel summary
     check_sync: int = 0              # >0: assert cross-rank parameter equality every N epochs (and at start)
@@ -133,7 +133,7 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--world-size", type=int, default=None, help="number of ranks (default: GPU count)")
     ap.add_argument("--port", type=int, default=_D.port)
     ap.add_argument("--timeout", type=float, default=_D.timeout_s, help="process-group timeout in seconds")
-    ap.add_argument("--model", default=_D.model, choices=["netresdeep", "resnet50", "resnext50"])
+    ap.add_argument("--model", default=_D.model, choices=["netresdeep", "resnet50", "resnext50", "mobilenet"])
     ap.add_argument("--bucket-mb", type=float, default=_D.bucket_mb, help="gradient bucket cap (generic DDP path)")
     ap.add_argument("--profile", default=_D.profile, metavar="DIR", help="write torch.profiler traces to DIR")
     ap.add_argument("--check-sync", type=int, default=_D.check_sync, metavar="N",
@@ -417,7 +417,15 @@ def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False, ema=No
     return evaluate_model(model, data, labels, cfg.dtype, kernel=kernel, ema=ema)
 
 
-RESNET_MODELS = {"resnet50": "resnet50", "resnext50": "resnext50_32x4d"}  # --model -> models/resnet50.py constructor
+# --model -> constructor of the generic path: a name of models/resnet50.py, or "module:name" under models/
+RESNET_MODELS = {"resnet50": "resnet50", "resnext50": "resnext50_32x4d", "mobilenet": "mobilenet:mobilenet"}
+
+
+def generic_model(name: str, num_classes: int = 10):
+    """The ``--model`` values of the generic path (``RESNET_MODELS``) -> a freshly constructed module."""
+    import importlib
+    mod, _, fn = RESNET_MODELS[name].rpartition(":")
+    return getattr(importlib.import_module(f"{__package__}.models.{mod or 'resnet50'}"), fn)(num_classes=num_classes)
 
 
 def eval_only(cfg: TrainConfig, device: torch.device, rank: int = 0):
@@ -426,8 +434,7 @@ def eval_only(cfg: TrainConfig, device: torch.device, rank: int = 0):
     if not cfg.resume:
         raise ValueError("--eval-only requires --resume")
     if cfg.model in RESNET_MODELS:
-        from .models import resnet50 as _rn
-        model = getattr(_rn, RESNET_MODELS[cfg.model])(num_classes=10).to(device)
+        model = generic_model(cfg.model).to(device)
     else:
         model = NetResDeep().to(device)
     load_checkpoint(model, cfg.resume, strict=True, map_location=device)
@@ -613,9 +620,8 @@ def build_model_for_rank(cfg: TrainConfig, rank: int, world_size: int, device: t
     FlatBucketDDP (``--model resnet50`` trains a 10-class ResNet-50 on the CIFAR tensors, channels-last, bf16)."""
     from .models.netresdeep import NetResDeep
     if cfg.model in RESNET_MODELS:
-        from .models import resnet50 as _rn
         torch.manual_seed(cfg.seed)
-        model = getattr(_rn, RESNET_MODELS[cfg.model])(num_classes=10).to(device)
+        model = generic_model(cfg.model).to(device)
         if device.type == "cuda":
             model = model.to(memory_format=torch.channels_last)
         if cfg.engine == "fused":

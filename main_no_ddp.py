@@ -20,7 +20,7 @@ import torch
 from distributeddataparallel_cifar10_amd.data.loader import DeviceLoader  # noqa: F401
 from distributeddataparallel_cifar10_amd.models.netresdeep import NetResDeep
 from distributeddataparallel_cifar10_amd.train import TrainConfig, add_cli_args, config_from_args, load_dataset
-from distributeddataparallel_cifar10_amd.train import eval_only, make_train_loader, wrap_model
+from distributeddataparallel_cifar10_amd.train import RESNET_MODELS, eval_only, generic_model, make_train_loader, wrap_model
 from distributeddataparallel_cifar10_amd.train import train_loop as _train_loop
 
 data_path = '../data/CIFAR-10/'  # reference main_no_ddp.py:17
@@ -64,10 +64,9 @@ if __name__ == "__main__":
     if _cfg.eval_only:  # --eval-only --resume CKPT: the checkpoint's test accuracy; no training
         eval_only(_cfg, device)
         raise SystemExit(0)
-    if _cfg.model in ("resnet50", "resnext50"):
-        from distributeddataparallel_cifar10_amd.models.resnet50 import resnet50, resnext50_32x4d
+    if _cfg.model in RESNET_MODELS:
         torch.manual_seed(_cfg.seed)
-        model = (resnet50 if _cfg.model == "resnet50" else resnext50_32x4d)(num_classes=10).to(device)
+        model = generic_model(_cfg.model).to(device)
     else:
         model = NetResDeep().to(device)
     train_loader = prepare()

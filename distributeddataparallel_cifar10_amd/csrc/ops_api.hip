@@ -194,6 +194,7 @@ using namespace dca::ops;
 #include "ops_roi.hip"
 #include "ops_gconv.hip"
 #include "ops_dwconv.hip"
+#include "ops_se.hip"
 
 namespace {
 thread_local GemmRoute g_route = {};      // of this thread's last dca_ops_gemm (dca_ops_gemm_last_route)
@@ -203,7 +204,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 19; }
+int dca_ops_abi_version() { return 20; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -1004,6 +1005,82 @@ int dca_ops_dwconv_wgrad(const void* x, const void* dy, float* ws, int slabs, fl
   hipLaunchKernelGGL(k_dwconv_wgrad_reduce, dim3((C * 9 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const float*)ws, dw, C, used, beta);
   OPCK(hipGetLastError());
+  return 0;
+}
+
+// Squeeze-and-excitation (ops_se.hip).  u / idt / out / dout / didt / du: dense NHWC bf16 [N][H][W][C]; z / dz: fp32
+// [N][C] gate logits; s / ds: [N][C], bf16 or fp32 by flag.
+static const char* se_rule(int N, int H, int W, int C) {
+  static const char* rule =
+      "se: the squeeze-and-excitation rule is dense NHWC bf16 with N, H, W, C >= 1, C % 8 == 0 and fewer than 2^31 "
+      "elements";
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return rule;
+  if ((long)N * H * W * C >= (1L << 31)) return rule;  // (P = H W and N x slabs fit an int)
+  return nullptr;
+}
+int dca_ops_se_rule(int N, int H, int W, int C) {
+  const char* e = se_rule(N, H, W, C);
+  REQUIRE(!e, e);
+  return 0;
+}
+// log2 of the chunks per slab (ops_se.hip, SePlan): the lanes (256 / CH) do not outnumber the pixels, and a slab is no
+// wider than the channels fill twice
+static int se_lc(int P, int C) { return P <= 64 && C >= 256 ? 5 : (P <= 256 && C >= 128 ? 4 : 3); }
+#define SE_LAUNCH(K, P, C, N, stream, ...)                                                                        \
+  do {                                                                                                            \
+    const int lc_ = se_lc(P, C);                                                                                  \
+    const dim3 grid_((unsigned)(N) * (unsigned)(((C) + (8 << lc_) - 1) / (8 << lc_)));                            \
+    if (lc_ == 5) hipLaunchKernelGGL((K<5>), grid_, dim3(SE_NT), 0, (hipStream_t)(stream), __VA_ARGS__);          \
+    else if (lc_ == 4) hipLaunchKernelGGL((K<4>), grid_, dim3(SE_NT), 0, (hipStream_t)(stream), __VA_ARGS__);     \
+    else hipLaunchKernelGGL((K<3>), grid_, dim3(SE_NT), 0, (hipStream_t)(stream), __VA_ARGS__);                   \
+    OPCK(hipGetLastError());                                                                                      \
+  } while (0)
+#define SE_ALIGNED(p) ((uintptr_t)(p) % 16 == 0)
+
+// s[n][c] = mean over the H W pixels of u (out_bf16: bf16, else fp32)
+int dca_ops_se_squeeze(const void* u, void* s, int out_bf16, int N, int H, int W, int C, void* stream) {
+  const char* e = se_rule(N, H, W, C);
+  REQUIRE(!e, e);
+  REQUIRE(u && s, "se_squeeze: buffer missing");
+  REQUIRE(SE_ALIGNED(u) && SE_ALIGNED(s), "se_squeeze: misaligned buffer");
+  SE_LAUNCH(k_se_squeeze, H * W, C, N, stream, (const bf16_t*)u, s, H * W, C, out_bf16);
+  return 0;
+}
+
+// out = ReLU(u * sigmoid(z)[n][c] + idt)
+int dca_ops_se_scale_fwd(const void* u, const float* z, const void* idt, void* out, int N, int H, int W, int C,
+                         void* stream) {
+  const char* e = se_rule(N, H, W, C);
+  REQUIRE(!e, e);
+  REQUIRE(u && z && idt && out, "se_scale_fwd: buffer missing");
+  REQUIRE(SE_ALIGNED(u) && SE_ALIGNED(idt) && SE_ALIGNED(out) && SE_ALIGNED(z), "se_scale_fwd: misaligned buffer");
+  SE_LAUNCH(k_se_scale_fwd, H * W, C, N, stream, (const bf16_t*)u, z, (const bf16_t*)idt, (bf16_t*)out, H * W, C);
+  return 0;
+}
+
+// didt = dout * [out > 0]; dz[n][c] = g (1 - g) sum over the pixels of didt * u
+int dca_ops_se_bwd_reduce(const void* dout, const void* out, const void* u, const float* z, void* didt, float* dz,
+                          int N, int H, int W, int C, void* stream) {
+  const char* e = se_rule(N, H, W, C);
+  REQUIRE(!e, e);
+  REQUIRE(dout && out && u && z && didt && dz, "se_bwd_reduce: buffer missing");
+  REQUIRE(SE_ALIGNED(dout) && SE_ALIGNED(out) && SE_ALIGNED(u) && SE_ALIGNED(didt) && SE_ALIGNED(z) && SE_ALIGNED(dz),
+          "se_bwd_reduce: misaligned buffer");
+  SE_LAUNCH(k_se_bwd_reduce, H * W, C, N, stream, (const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)u, z,
+            (bf16_t*)didt, dz, H * W, C);
+  return 0;
+}
+
+// du = dout * [out > 0] * g[n][c] + ds[n][c] / (H W) (ds_bf16: ds is bf16, else fp32)
+int dca_ops_se_bwd_apply(const void* dout, const void* out, const float* z, const void* ds, int ds_bf16, void* du,
+                         int N, int H, int W, int C, void* stream) {
+  const char* e = se_rule(N, H, W, C);
+  REQUIRE(!e, e);
+  REQUIRE(dout && out && z && ds && du, "se_bwd_apply: buffer missing");
+  REQUIRE(SE_ALIGNED(dout) && SE_ALIGNED(out) && SE_ALIGNED(du) && SE_ALIGNED(z) && SE_ALIGNED(ds),
+          "se_bwd_apply: misaligned buffer");
+  SE_LAUNCH(k_se_bwd_apply, H * W, C, N, stream, (const bf16_t*)dout, (const bf16_t*)out, z, ds, (bf16_t*)du, H * W, C,
+            ds_bf16);
   return 0;
 }
 

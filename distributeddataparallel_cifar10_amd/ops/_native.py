@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 _lock = threading.Lock()
 _lib = None
 
@@ -184,9 +184,23 @@ DWCONV_ENTRY_POINTS = {
 }
 
 
+# Squeeze-and-excitation (csrc/ops_se.hip), run on the GPU by tests/test_ops_se_gpu.py.  z / dz: fp32 [N, C] gate logits.
+SE_ENTRY_POINTS = {
+    "dca_ops_se_rule": [c_int] * 4,  # N, H, W, C
+    # u, s, out_bf16, N, H, W, C, stream
+    "dca_ops_se_squeeze": [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+    # u, z, idt, out, N, H, W, C, stream
+    "dca_ops_se_scale_fwd": [c_void_p] * 4 + [c_int] * 4 + [c_void_p],
+    # dout, out, u, z, didt, dz, N, H, W, C, stream
+    "dca_ops_se_bwd_reduce": [c_void_p] * 6 + [c_int] * 4 + [c_void_p],
+    # dout, out, z, ds, ds_bf16, du, N, H, W, C, stream
+    "dca_ops_se_bwd_apply": [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 4 + [c_void_p],
+}
+
+
 def _declare_later(lib):
     for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS,
-                           **DWCONV_ENTRY_POINTS}.items():
+                           **DWCONV_ENTRY_POINTS, **SE_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

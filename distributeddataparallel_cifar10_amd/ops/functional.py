@@ -1399,6 +1399,161 @@ def global_avg_pool(x, out_dtype=torch.float32):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# Squeeze-and-excitation (csrc/ops_se.hip): s = mean_p u; out = ReLU(u * sigmoid(z) + idt) with z = the gate MLP of s
+# (``linear`` twice).  The shape rule lives in the launchers (dca_ops_se_rule, device-free).
+# ------------------------------------------------------------------------------------------------------------
+def se_check(shape) -> None:
+    dims = [int(v) for v in shape]
+    if len(dims) != 4 or max(dims) >= 2 ** 31:
+        dims = [0, 0, 0, 0]  # (no shape the rule takes)
+    if N.lib().dca_ops_se_rule(*dims) != 0:
+        raise ValueError(f"se: input {tuple(shape)}: {N.lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def _se_operand(t, shape, name, dtype=torch.bfloat16) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"se: {name} is a contiguous {dtype} tensor of shape {tuple(shape)}, "
+                         f"got {t.dtype} {tuple(t.shape)}")
+
+
+class SELink:
+    """Ties the ``se_squeeze`` and the ``se_scale`` of one SE block, which share the input u.  du has a pooling term
+    (ds / P, through the squeeze) and a gate term (dout * mask * g, through the scale); se_scale's backward returns
+    no gradient for u and leaves (dout, out, z) here, and se_squeeze's backward, which autograd runs once ds is known,
+    writes du with both terms in one kernel.  One use per forward, in this order: squeeze, scale, scale's backward,
+    squeeze's backward."""
+    STEPS = ("se_squeeze", "se_scale", "se_scale's backward", "se_squeeze's backward")
+
+    def __init__(self):
+        self.step = 0
+        self.shape = None
+        self.saved = None  # (dout, out, z) between the two backwards
+
+    def advance(self, step: int) -> None:
+        if self.step != step:
+            raise RuntimeError(f"SELink: {self.STEPS[step]} came when "
+                               f"{self.STEPS[self.step] if self.step < 4 else 'nothing more'} was due (a link serves "
+                               "one squeeze and one scale of the same input, once)")
+        self.step += 1
+
+
+def se_squeeze_fwd(u, out_dtype=torch.bfloat16):
+    """s [N, C] (bf16 or fp32) = the mean over H, W of NHWC bf16 u."""
+    se_check(u.shape)
+    _dev_check(u)
+    _se_operand(u, u.shape, "u")
+    n, h, w, c = u.shape
+    s = torch.empty(n, c, dtype=out_dtype, device=u.device)
+    N.check(N.lib().dca_ops_se_squeeze(N.ptr(u), N.ptr(s), int(out_dtype == torch.bfloat16), n, h, w, c,
+                                       N.stream(u.device)), "se_squeeze")
+    return s
+
+
+def se_scale_fwd(u, z, idt):
+    """out = ReLU(u * sigmoid(z)[n, c] + idt) in bf16: u, idt NHWC bf16, z fp32 [N, C]."""
+    se_check(u.shape)
+    _dev_check(u, z, idt)
+    n, h, w, c = u.shape
+    _se_operand(u, u.shape, "u")
+    _se_operand(idt, u.shape, "idt")
+    _se_operand(z, (n, c), "z", torch.float32)
+    out = torch.empty_like(u)
+    N.check(N.lib().dca_ops_se_scale_fwd(N.ptr(u), N.ptr(z), N.ptr(idt), N.ptr(out), n, h, w, c, N.stream(u.device)),
+            "se_scale_fwd")
+    return out
+
+
+def se_bwd_reduce(dout, out, u, z):
+    """(didt, dz): didt = dout * [out > 0] (bf16), dz [N, C] fp32 = g (1 - g) sum_p didt * u, in one pass."""
+    se_check(u.shape)
+    _dev_check(dout, out, u, z)
+    n, h, w, c = u.shape
+    for t, name in ((dout, "dout"), (out, "out"), (u, "u")):
+        _se_operand(t, u.shape, name)
+    _se_operand(z, (n, c), "z", torch.float32)
+    didt = torch.empty_like(u)
+    dz = torch.empty(n, c, dtype=torch.float32, device=u.device)
+    N.check(N.lib().dca_ops_se_bwd_reduce(N.ptr(dout), N.ptr(out), N.ptr(u), N.ptr(z), N.ptr(didt), N.ptr(dz), n, h, w,
+                                          c, N.stream(u.device)), "se_bwd_reduce")
+    return didt, dz
+
+
+def se_bwd_apply(dout, out, z, ds):
+    """du = dout * [out > 0] * sigmoid(z)[n, c] + ds[n, c] / (H W) in bf16; ds [N, C] bf16 or fp32."""
+    se_check(dout.shape)
+    _dev_check(dout, out, z, ds)
+    n, h, w, c = dout.shape
+    _se_operand(dout, dout.shape, "dout")
+    _se_operand(out, dout.shape, "out")
+    _se_operand(z, (n, c), "z", torch.float32)
+    if ds.dtype != torch.bfloat16:
+        ds = ds.float()
+    ds = ds.contiguous()
+    _se_operand(ds, (n, c), "ds", ds.dtype)
+    du = torch.empty_like(dout)
+    N.check(N.lib().dca_ops_se_bwd_apply(N.ptr(dout), N.ptr(out), N.ptr(z), N.ptr(ds), int(ds.dtype == torch.bfloat16),
+                                         N.ptr(du), n, h, w, c, N.stream(dout.device)), "se_bwd_apply")
+    return du
+
+
+class _SESqueeze(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, link):
+        link.advance(0)
+        link.shape = tuple(u.shape)
+        ctx.link = link
+        return se_squeeze_fwd(u)
+
+    @staticmethod
+    def backward(ctx, ds):
+        link, ctx.link = ctx.link, None
+        link.advance(3)
+        (dout, out, z), link.saved = link.saved, None
+        return se_bwd_apply(dout, out, z, ds), None
+
+
+class _SEScale(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, z, idt, link, x_join):
+        link.advance(1)
+        if tuple(u.shape) != link.shape:
+            raise ValueError(f"se_scale: the link's squeeze saw an input of shape {link.shape}, this one is "
+                             f"{tuple(u.shape)}")
+        z = z.contiguous()
+        out = se_scale_fwd(u, z, idt)
+        ctx.save_for_backward(u, z, out)
+        ctx.link, ctx.x_join = link, x_join
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        u, z, out = ctx.saved_tensors
+        link, x_join, ctx.link, ctx.x_join = ctx.link, ctx.x_join, None, None
+        link.advance(2)
+        dout = dout.to(torch.bfloat16).contiguous()
+        didt, dz = se_bwd_reduce(dout, out, u, z)
+        link.saved = (dout, out, z)
+        if x_join is not None:  # the identity gradient seeds the block input's shared buffer (conv1's dgrad adds to it)
+            didt = x_join.contribute(didt)
+        return None, dz, didt, None, None
+
+
+def se_squeeze(u, link: SELink):
+    """s [N, C] bf16 (the gate MLP's GEMM operand) = the mean over H, W of NHWC bf16 u.  Its backward writes the whole
+    du, gate term included (``SELink``)."""
+    return _SESqueeze.apply(u, link)
+
+
+def se_scale(u, z, idt, link: SELink, x_join: Optional[GradJoin] = None):
+    """ReLU(u * sigmoid(z)[n, c] + idt) in bf16 for NHWC bf16 u and idt and fp32 gate logits z [N, C]; ``link``: the one
+    of ``se_squeeze(u, link)``.  x_join: idt is also consumed elsewhere (a block input, ``GradJoin`` without deferral):
+    its gradient is the join's first contribution."""
+    if x_join is not None and x_join.defer_ok:
+        raise ValueError("se_scale: the identity gradient is written, so its join cannot defer a masked source")
+    return _SEScale.apply(u, z, idt, link, x_join if torch.is_grad_enabled() else None)
+
+
+# ------------------------------------------------------------------------------------------------------------
 # ROI-align (csrc/ops_roi.hip): one launch each way; the backward is a gather with a fixed summation order
 # ------------------------------------------------------------------------------------------------------------
 def roi_align_ok(feat: torch.Tensor, bins: int, n_boxes: int = 0, stride: float = 16.0) -> bool:

@@ -19,6 +19,8 @@ switches to channels-last bf16 once, and runs:
   weights are quantised per step (WeightPack, device-side amax); activations are emitted in
   fp8 directly by the producing BN kernel with delayed scaling (previous step's amax, ``functional.Fp8Delayed``);
   gradients and the backward stay bf16 (BASELINE config 5).
+  Squeeze-and-excitation bottlenecks (``se_reduction``: SE-ResNet-50, SE-ResNeXt-50) end in bn3 (plain) -> squeeze
+  (csrc/ops_se.hip) -> fc1 + ReLU -> fc2 -> ReLU(u * sigmoid(z) + identity) (csrc/ops_se.hip); bf16 only.
 * MobileNetV1: the ResNet entry (``begin``: 8-channel NHWC input, one pack launch), then the 3x3/2 stem (dense implicit
   GEMM) and 13 x [depthwise 3x3 (csrc/ops_dwconv.hip) -> BN + ReLU -> 1x1 -> BN + ReLU], every conv with its BN
   statistics from the conv kernel, -> global average pool -> fc.
@@ -52,6 +54,8 @@ class OpsModel(nn.Module):
         self.module = model
         self.fp8 = fp8
         self.kind = "netresdeep" if _is_netresdeep(model) else ("mobilenet" if _is_mobilenet(model) else "resnet")
+        if fp8 and any(getattr(m, "se", None) is not None for m in model.modules()):
+            raise ValueError("OpsModel: fp8 is not available for a squeeze-and-excitation model (its blocks run bf16)")
         self._pack = None
         self._s2d = None
 
@@ -162,6 +166,9 @@ class OpsModel(nn.Module):
         """Bottleneck blocks in sequence over NHWC bf16 ``h``."""
         blocks = list(blocks)
         for i, b in enumerate(blocks):
+            if getattr(b, "se", None) is not None:
+                h = self._se_block(h, b)
+                continue
             nxt = blocks[i + 1].conv1 if i + 1 < len(blocks) else None
             # the block input feeds conv1 and the identity / downsample path: one shared gradient buffer
             c1 = b.conv1
@@ -183,6 +190,25 @@ class OpsModel(nn.Module):
             h = self._conv_bn(out, b.conv3, b.bn3, relu=True, r=idt, consumer=nxt,
                               r_join=join if b.downsample is None else rlink)  # relu(bn3(conv3) + identity)
         return h
+
+    def _se_block(self, h, b):
+        """A squeeze-and-excitation bottleneck: relu(bn3(conv3) * sigmoid(fc2(relu(fc1(mean)))) + identity).  bn3 runs
+        plain (no residual, no ReLU); the join is csrc/ops_se.hip's, so neither the masked-join deferral nor a
+        ResidualLink applies: the identity gradient is written by se_scale's backward and, in an identity block, seeds
+        the block input's shared gradient buffer."""
+        join = F.GradJoin(2)
+        if b.downsample is None:
+            idt = h
+        else:
+            idt = self._conv_bn(h, b.downsample[0], b.downsample[1], relu=False, x_join=join)
+        out = self._conv_bn(h, b.conv1, b.bn1, x_join=join)
+        out = self._conv_bn(out, b.conv2, b.bn2)
+        u = self._conv_bn(out, b.conv3, b.bn3, relu=False)
+        link = F.SELink()
+        s = F.se_squeeze(u, link)
+        s = F.linear(s, b.se.fc1.weight, b.se.fc1.bias, relu=True, out_dtype=torch.bfloat16)
+        z = F.linear(s, b.se.fc2.weight, b.se.fc2.bias, out_dtype=torch.float32)
+        return F.se_scale(u, z, idt, link, x_join=join if b.downsample is None else None)
 
     def head(self, h, fc):
         """Global average pool -> fc (fp32 logits)."""

@@ -195,6 +195,7 @@ using namespace dca::ops;
 #include "ops_gconv.hip"
 #include "ops_dwconv.hip"
 #include "ops_se.hip"
+#include "ops_attn.hip"
 
 namespace {
 thread_local GemmRoute g_route = {};      // of this thread's last dca_ops_gemm (dca_ops_gemm_last_route)
@@ -204,7 +205,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 20; }
+int dca_ops_abi_version() { return 21; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -1081,6 +1082,51 @@ int dca_ops_se_bwd_apply(const void* dout, const void* out, const float* z, cons
           "se_bwd_apply: misaligned buffer");
   SE_LAUNCH(k_se_bwd_apply, H * W, C, N, stream, (const bf16_t*)dout, (const bf16_t*)out, z, ds, (bf16_t*)du, H * W, C,
             ds_bf16);
+  return 0;
+}
+
+
+// Fused multi-head self-attention (ops_attn.hip).  qkv / dqkv: bf16 [B][L][3][H][D]; o / dout: bf16 [B][L][H][D]; lse:
+// fp32 [B][H][L].
+static const char* attn_rule(int B, int L, int H, int D) {
+  static const char* rule =
+      "attn: the attention rule is dense bf16 qkv [B, L, 3, H, D] with D == 64, 1 <= L <= 256, B, H >= 1 and fewer "
+      "than 2^31 elements";
+  if (B <= 0 || H <= 0 || D != 64 || L < 1 || L > 256) return rule;
+  if ((long)B * L * 3 * H * D >= (1L << 31)) return rule;  // (B * H fits the grid, element offsets fit 32 bits)
+  return nullptr;
+}
+int dca_ops_attn_rule(int B, int L, int H, int D) {
+  const char* e = attn_rule(B, L, H, D);
+  REQUIRE(!e, e);
+  return 0;
+}
+#define ATTN_ALIGNED(p) ((uintptr_t)(p) % 16 == 0)
+// o = softmax(scale q k^T) v per (b, h), lse = the rows' log-sum-exp of the scaled scores
+int dca_ops_attn_fwd(const void* qkv, void* o, float* lse, int B, int L, int H, int D, float scale, void* stream) {
+  const char* e = attn_rule(B, L, H, D);
+  REQUIRE(!e, e);
+  REQUIRE(qkv && o && lse, "attn_fwd: buffer missing");
+  REQUIRE(ATTN_ALIGNED(qkv) && ATTN_ALIGNED(o) && ATTN_ALIGNED(lse), "attn_fwd: misaligned buffer");
+  if (L <= 96) OPCK(at_fwd_launch<3>(qkv, o, lse, B, L, H, scale, stream));
+  else if (L <= 224) OPCK(at_fwd_launch<7>(qkv, o, lse, B, L, H, scale, stream));
+  else OPCK(at_fwd_launch<8>(qkv, o, lse, B, L, H, scale, stream));
+  return 0;
+}
+
+// dqkv (every element written once) from the forward's operands, o, lse and dout
+int dca_ops_attn_bwd(const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv, int B, int L,
+                     int H, int D, float scale, void* stream) {
+  const char* e = attn_rule(B, L, H, D);
+  REQUIRE(!e, e);
+  REQUIRE(qkv && o && lse && dout && dqkv, "attn_bwd: buffer missing");
+  REQUIRE(ATTN_ALIGNED(qkv) && ATTN_ALIGNED(o) && ATTN_ALIGNED(lse) && ATTN_ALIGNED(dout) && ATTN_ALIGNED(dqkv),
+          "attn_bwd: misaligned buffer");
+  const int lds = at_bwd_lds(L);
+  OPCK(hipFuncSetAttribute((const void*)k_attn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(k_attn_bwd, dim3((unsigned)B * (unsigned)H), dim3(AT_NT), lds, (hipStream_t)stream,
+                     (const bf16_t*)qkv, (const bf16_t*)o, lse, (const bf16_t*)dout, (bf16_t*)dqkv, L, H, scale);
+  OPCK(hipGetLastError());
   return 0;
 }
 

@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 _lock = threading.Lock()
 _lib = None
 
@@ -198,9 +198,20 @@ SE_ENTRY_POINTS = {
 }
 
 
+# Fused multi-head self-attention (csrc/ops_attn.hip), run on the GPU by tests/test_ops_attn_gpu.py.  qkv / dqkv: bf16
+# [B, L, 3, H, D]; o / dout: bf16 [B, L, H, D]; lse: fp32 [B, H, L].
+ATTN_ENTRY_POINTS = {
+    "dca_ops_attn_rule": [c_int] * 4,  # B, L, H, D
+    # qkv, o, lse, B, L, H, D, scale, stream
+    "dca_ops_attn_fwd": [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p],
+    # qkv, o, lse, dout, dqkv, B, L, H, D, scale, stream
+    "dca_ops_attn_bwd": [c_void_p] * 5 + [c_int] * 4 + [c_float, c_void_p],
+}
+
+
 def _declare_later(lib):
     for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS,
-                           **DWCONV_ENTRY_POINTS, **SE_ENTRY_POINTS}.items():
+                           **DWCONV_ENTRY_POINTS, **SE_ENTRY_POINTS, **ATTN_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

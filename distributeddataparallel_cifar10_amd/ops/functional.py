@@ -1554,6 +1554,99 @@ def se_scale(u, z, idt, link: SELink, x_join: Optional[GradJoin] = None):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# Fused multi-head self-attention (csrc/ops_attn.hip): one launch each way on the qkv linear's output; the backward
+# recomputes the probabilities from the saved row log-sum-exp.  The shape rule lives in the launchers
+# (dca_ops_attn_rule, device-free).
+# ------------------------------------------------------------------------------------------------------------
+def attn_check(shape) -> None:
+    """``shape``: (B, L, H, D) of a qkv tensor [B, L, 3, H, D]."""
+    dims = [int(v) for v in shape]
+    if len(dims) != 4 or max(dims) >= 2 ** 31 or min(dims) < 0:
+        dims = [0, 0, 0, 0]  # (no shape the rule takes)
+    if N.lib().dca_ops_attn_rule(*dims) != 0:
+        raise ValueError(f"attention: (B, L, H, D) = {tuple(shape)}: "
+                         f"{N.lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def _attn_operand(t, shape, name, dtype=torch.bfloat16) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"attention: {name} is a contiguous {dtype} tensor of shape {tuple(shape)}, "
+                         f"got {t.dtype} {tuple(t.shape)}")
+
+
+def _attn_dims(qkv):
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise ValueError(f"attention: qkv is [B, L, 3, H, D], got {tuple(qkv.shape)}")
+    b, l, _, h, d = qkv.shape
+    attn_check((b, l, h, d))
+    return b, l, h, d
+
+
+def attention_fwd(qkv, scale):
+    """(o [B, L, H, D] bf16, lse [B, H, L] fp32) = softmax(scale q k^T) v per head of qkv [B, L, 3, H, D] bf16."""
+    b, l, h, d = _attn_dims(qkv)
+    _dev_check(qkv)
+    _attn_operand(qkv, qkv.shape, "qkv")
+    o = torch.empty(b, l, h, d, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(b, h, l, dtype=torch.float32, device=qkv.device)
+    N.check(N.lib().dca_ops_attn_fwd(N.ptr(qkv), N.ptr(o), N.ptr(lse), b, l, h, d, float(scale),
+                                     N.stream(qkv.device)), "attn_fwd")
+    return o, lse
+
+
+def attention_bwd(qkv, o, lse, dout, scale):
+    """dqkv [B, L, 3, H, D] bf16 (every element written) from the forward's qkv, o, lse and dout [B, L, H, D] bf16."""
+    b, l, h, d = _attn_dims(qkv)
+    _dev_check(qkv, o, lse, dout)
+    _attn_operand(qkv, qkv.shape, "qkv")
+    _attn_operand(o, (b, l, h, d), "o")
+    _attn_operand(dout, (b, l, h, d), "dout")
+    _attn_operand(lse, (b, h, l), "lse", torch.float32)
+    dqkv = torch.empty_like(qkv)
+    N.check(N.lib().dca_ops_attn_bwd(N.ptr(qkv), N.ptr(o), N.ptr(lse), N.ptr(dout), N.ptr(dqkv), b, l, h, d,
+                                     float(scale), N.stream(qkv.device)), "attn_bwd")
+    return dqkv
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, scale):
+        o, lse = attention_fwd(qkv, scale)
+        ctx.save_for_backward(qkv, o, lse)  # (under no_grad autograd keeps none of them)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        qkv, o, lse = ctx.saved_tensors
+        return attention_bwd(qkv, o, lse, dout.to(torch.bfloat16).contiguous(), ctx.scale), None
+
+
+def attention(qkv: torch.Tensor, heads: int, scale: Optional[float] = None) -> torch.Tensor:
+    """Multi-head self-attention softmax(scale q k^T) v (no mask, no dropout) on the output of the qkv linear:
+    ``qkv`` [B, L, 3 * heads * D] or [B, L, 3, heads, D], bf16, CUDA, contiguous, D = 64, L <= 256 -> [B, L, heads * D]
+    bf16, the input of the projection linear.  ``scale`` defaults to D ** -0.5."""
+    if not isinstance(qkv, torch.Tensor) or qkv.dtype != torch.bfloat16:
+        raise TypeError(f"attention: qkv is a bfloat16 tensor, got {getattr(qkv, 'dtype', type(qkv))}")
+    _dev_check(qkv)
+    heads = int(heads)
+    if qkv.dim() == 3:
+        if heads <= 0 or qkv.shape[2] % (3 * heads):
+            raise ValueError(f"attention: the last dimension {qkv.shape[2]} is not 3 * {heads} heads * D")
+        if not qkv.is_contiguous():
+            raise ValueError("attention: qkv is contiguous")
+        qkv = qkv.view(qkv.shape[0], qkv.shape[1], 3, heads, qkv.shape[2] // (3 * heads))
+    elif qkv.dim() != 5 or qkv.shape[2] != 3 or qkv.shape[3] != heads:
+        raise ValueError(f"attention: qkv is [B, L, 3 * {heads} * D] or [B, L, 3, {heads}, D], got {tuple(qkv.shape)}")
+    if not qkv.is_contiguous():
+        raise ValueError("attention: qkv is contiguous")
+    b, l, h, d = _attn_dims(qkv)
+    o = _Attention.apply(qkv, float(d ** -0.5 if scale is None else scale))
+    return o.view(b, l, h * d)
+
+
+# ------------------------------------------------------------------------------------------------------------
 # ROI-align (csrc/ops_roi.hip): one launch each way; the backward is a gather with a fixed summation order
 # ------------------------------------------------------------------------------------------------------------
 def roi_align_ok(feat: torch.Tensor, bins: int, n_boxes: int = 0, stride: float = 16.0) -> bool:

@@ -1,7 +1,7 @@
 """Model forwards on the ops layer (HIP kernels for every layer), sharing the parameters of the torch modules.
 
-``OpsModel(model)`` wraps a ``NetResDeep`` (reference ``model/resnet.py``), a ResNet (``models/resnet50.py``) or a
-MobileNetV1 (``models/mobilenet.py``) without copying anything: the wrapped module's ``nn.Parameter``s and BN buffers are the ones the kernels read
+``OpsModel(model)`` wraps a ``NetResDeep`` (reference ``model/resnet.py``), a ResNet (``models/resnet50.py``), a
+MobileNetV1 (``models/mobilenet.py``) or a VisionTransformer (``models/vit.py``) without copying anything: the wrapped module's ``nn.Parameter``s and BN buffers are the ones the kernels read
 and the optimizer updates, so ``state_dict()`` is unchanged.  The forward takes the usual NCHW fp32 batch,
 switches to channels-last bf16 once, and runs:
 
@@ -24,6 +24,12 @@ switches to channels-last bf16 once, and runs:
 * MobileNetV1: the ResNet entry (``begin``: 8-channel NHWC input, one pack launch), then the 3x3/2 stem (dense implicit
   GEMM) and 13 x [depthwise 3x3 (csrc/ops_dwconv.hip) -> BN + ReLU -> 1x1 -> BN + ReLU], every conv with its BN
   statistics from the conv kernel, -> global average pool -> fc.
+* VisionTransformer: the patch embedding as a reshape of the input into [B L', 3 p p] rows and ``linear`` on the conv
+  weight viewed as a matrix, then per block qkv ``linear`` -> ``attention`` (csrc/ops_attn.hip, directly on the qkv
+  linear's [B, L, 3 H 64] output) -> proj ``linear``, and the MLP's two ``linear``s; bf16 between layers, fp32 logits.
+  Stated scope: LayerNorm, GELU, the residual adds and the position-embedding add are torch operations on bf16
+  tensors (as ``DCA_OPS_ROI=0`` also mixes torch autograd with ops functions); bf16 only.  A head width or sequence
+  length outside the attention rule raises the rule's ``ValueError`` at the first forward.
 """
 from __future__ import annotations
 
@@ -48,12 +54,20 @@ def _is_mobilenet(m: nn.Module) -> bool:
             and all(hasattr(b, "dw") and hasattr(b, "pw") for b in m.blocks))
 
 
+def _is_vit(m: nn.Module) -> bool:
+    return all(hasattr(m, a) for a in ("patch_embed", "cls_token", "pos_embed", "blocks", "norm", "head"))
+
+
 class OpsModel(nn.Module):
     def __init__(self, model: nn.Module, fp8: bool = False):
         super().__init__()
         self.module = model
         self.fp8 = fp8
         self.kind = "netresdeep" if _is_netresdeep(model) else ("mobilenet" if _is_mobilenet(model) else "resnet")
+        if _is_vit(model):
+            self.kind = "vit"
+            if fp8:
+                raise ValueError("OpsModel: fp8 is not available for a vision transformer (its layers run bf16)")
         if fp8 and any(getattr(m, "se", None) is not None for m in model.modules()):
             raise ValueError("OpsModel: fp8 is not available for a squeeze-and-excitation model (its blocks run bf16)")
         self._pack = None
@@ -65,6 +79,8 @@ class OpsModel(nn.Module):
             return self._netresdeep(h)
         if self.kind == "mobilenet":
             return self._mobilenet(self.begin(x))
+        if self.kind == "vit":
+            return self._vit(x)
         return self._resnet(self.begin(x))
 
     def begin(self, x: torch.Tensor) -> torch.Tensor:
@@ -228,3 +244,29 @@ class OpsModel(nn.Module):
             h = self._conv_bn(h, b.dw, b.bn1, consumer=b.pw)
             h = self._conv_bn(h, b.pw, b.bn2)
         return self.head(h, m.fc)
+
+    def _vit(self, x):
+        """models/vit.py on ``linear`` and ``attention``; LayerNorm, GELU and the adds are torch operations on bf16
+        tensors (the module docstring's stated scope)."""
+        m, bf = self.module, torch.bfloat16
+        tnf = torch.nn.functional
+
+        def lin(h, layer, out_dtype=bf):
+            return F.linear(h, layer.weight, layer.bias, out_dtype=out_dtype)
+
+        def norm(h, ln):
+            return tnf.layer_norm(h, ln.normalized_shape, ln.weight.to(bf), ln.bias.to(bf), ln.eps)
+
+        n, c, hh, ww = x.shape
+        p, dim = m.patch, m.dim
+        rows = x.reshape(n, c, hh // p, p, ww // p, p).permute(0, 2, 4, 1, 3, 5).reshape(-1, c * p * p).to(bf)
+        tok = F.linear(rows, m.patch_embed.weight.reshape(dim, -1), m.patch_embed.bias, out_dtype=bf)
+        h = torch.cat([m.cls_token.to(bf).expand(n, -1, -1), tok.view(n, -1, dim)], dim=1) + m.pos_embed.to(bf)
+        seq = h.shape[1]
+        for b in m.blocks:
+            qkv = lin(norm(h, b.norm1).view(n * seq, dim), b.qkv)
+            a = F.attention(qkv.view(n, seq, 3 * dim), b.heads)
+            h = h + lin(a.view(n * seq, dim), b.proj).view(n, seq, dim)
+            z = tnf.gelu(lin(norm(h, b.norm2).view(n * seq, dim), b.fc1))
+            h = h + lin(z, b.fc2).view(n, seq, dim)
+        return lin(norm(h[:, 0], m.norm).contiguous(), m.head, out_dtype=torch.float32)

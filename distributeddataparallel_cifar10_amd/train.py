@@ -69,7 +69,7 @@ class TrainConfig:
     backend: str = "nccl"
     port: Optional[int] = None
     timeout_s: Optional[float] = None
-    # netresdeep | resnet50 | resnext50 | seresnet50 | seresnext50 | mobilenet (all but the first: the generic path)
+    # netresdeep | resnet50 | resnext50 | seresnet50 | seresnext50 | mobilenet | vit (all but the first: the generic path)
     model: str = "netresdeep"
     bucket_mb: float = 4.0           # FlatBucketDDP bucket cap (generic path)
     profile: Optional[str] = None    # directory for torch.profiler traces / kernel summary
@@ -135,7 +135,8 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--port", type=int, default=_D.port)
     ap.add_argument("--timeout", type=float, default=_D.timeout_s, help="process-group timeout in seconds")
     ap.add_argument("--model", default=_D.model,
-                    choices=["netresdeep", "resnet50", "resnext50", "seresnet50", "seresnext50", "mobilenet"])
+                    choices=["netresdeep", "resnet50", "resnext50", "seresnet50", "seresnext50", "mobilenet",
+                             "vit"])
     ap.add_argument("--bucket-mb", type=float, default=_D.bucket_mb, help="gradient bucket cap (generic DDP path)")
     ap.add_argument("--profile", default=_D.profile, metavar="DIR", help="write torch.profiler traces to DIR")
     ap.add_argument("--check-sync", type=int, default=_D.check_sync, metavar="N",
@@ -421,7 +422,7 @@ def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False, ema=No
 
 # --model -> constructor of the generic path: a name of models/resnet50.py, or "module:name" under models/
 RESNET_MODELS = {"resnet50": "resnet50", "resnext50": "resnext50_32x4d", "seresnet50": "se_resnet50",
-                 "seresnext50": "se_resnext50_32x4d", "mobilenet": "mobilenet:mobilenet"}
+                 "seresnext50": "se_resnext50_32x4d", "mobilenet": "mobilenet:mobilenet", "vit": "vit:vit_tiny"}
 
 
 def generic_model(name: str, num_classes: int = 10):

@@ -196,6 +196,7 @@ using namespace dca::ops;
 #include "ops_dwconv.hip"
 #include "ops_se.hip"
 #include "ops_attn.hip"
+#include "ops_ln.hip"
 
 namespace {
 thread_local GemmRoute g_route = {};      // of this thread's last dca_ops_gemm (dca_ops_gemm_last_route)
@@ -205,7 +206,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 21; }
+int dca_ops_abi_version() { return 22; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -1126,6 +1127,106 @@ int dca_ops_attn_bwd(const void* qkv, const void* o, const float* lse, const voi
   OPCK(hipFuncSetAttribute((const void*)k_attn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   hipLaunchKernelGGL(k_attn_bwd, dim3((unsigned)B * (unsigned)H), dim3(AT_NT), lds, (hipStream_t)stream,
                      (const bf16_t*)qkv, (const bf16_t*)o, lse, (const bf16_t*)dout, (bf16_t*)dqkv, L, H, scale);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Fused residual-add LayerNorm and GELU (ops_ln.hip).  Rows are bf16, gamma / beta the fp32 master parameters.
+static const char* ln_rule(long M, int C, int ldx) {
+  static const char* rule =
+      "ln: the LayerNorm rule is bf16 rows [M][ldx] of which the first C elements are read, with C % 8 == 0, "
+      "64 <= C <= 2048, ldx >= C, ldx % 8 == 0, M >= 1, fewer than 2^31 elements and 16-byte aligned bases";
+  if (C % 8 || C < 64 || C > 2048 || ldx < C || ldx % 8 || M < 1) return rule;
+  if (M * (long)ldx >= (1L << 31)) return rule;
+  return nullptr;
+}
+static const char* gelu_rule(long R, int N) {
+  static const char* rule =
+      "gelu: the GELU rule is dense bf16 [R][N] with N % 8 == 0, R, N >= 1, fewer than 2^31 elements and 16-byte "
+      "aligned bases";
+  if (R < 1 || N < 1 || N % 8 || R * (long)N >= (1L << 31)) return rule;
+  return nullptr;
+}
+int dca_ops_ln_rule(long M, int C, int ldx) {
+  const char* e = ln_rule(M, C, ldx);
+  REQUIRE(!e, e);
+  return 0;
+}
+int dca_ops_gelu_rule(long R, int N) {
+  const char* e = gelu_rule(R, N);
+  REQUIRE(!e, e);
+  return 0;
+}
+#define LN_ALIGNED(p) ((uintptr_t)(p) % 16 == 0)
+// x, delta (optional): rows of stride ldx; hsum (written only with delta), y: [M][C]; stats: fp32 [M][2] (mean, rstd);
+// max_wg: the most workgroups
+int dca_ops_ln_fwd(const void* x, const void* delta, const float* gamma, const float* beta, void* hsum, void* y,
+                   float* stats, long M, int C, int ldx, float eps, int max_wg, void* stream) {
+  const char* e = ln_rule(M, C, ldx);
+  REQUIRE(!e, e);
+  REQUIRE(x && gamma && beta && y && stats && (!delta || hsum) && max_wg >= 1, "ln_fwd: buffer missing");
+  REQUIRE(LN_ALIGNED(x) && LN_ALIGNED(delta) && LN_ALIGNED(gamma) && LN_ALIGNED(beta) && LN_ALIGNED(hsum) &&
+              LN_ALIGNED(y) && LN_ALIGNED(stats), e = ln_rule(0, 0, 0));
+  int G, cpl;
+  ln_pick(C, &G, &cpl);
+#define LN_CALL(g, c) OPCK((ln_fwd_launch<g, c>(x, delta, gamma, beta, hsum, y, stats, (int)M, C, ldx, eps, max_wg, stream)))
+  LN_DISPATCH(G, cpl, LN_CALL, REQUIRE(false, "ln_fwd: no kernel for this row width"));
+#undef LN_CALL
+  return 0;
+}
+
+// h: the forward's hsum (or its x when there was no delta), rows of stride ldh; dy, dres (optional), dx: [M][C];
+// part: slabs * 2 * C floats; dgb: fp32 [2][C] = (dgamma, dbeta)
+int dca_ops_ln_bwd(const void* h, int ldh, const void* dy, const void* dres, const float* gamma, const float* stats,
+                   void* dx, float* part, float* dgb, long M, int C, int slabs, void* stream) {
+  const char* e = ln_rule(M, C, ldh);
+  REQUIRE(!e, e);
+  REQUIRE(h && dy && gamma && stats && dx && part && dgb && slabs >= 1, "ln_bwd: buffer missing");
+  REQUIRE(LN_ALIGNED(h) && LN_ALIGNED(dy) && LN_ALIGNED(dres) && LN_ALIGNED(gamma) && LN_ALIGNED(stats) &&
+              LN_ALIGNED(dx) && LN_ALIGNED(part) && LN_ALIGNED(dgb), e = ln_rule(0, 0, 0));
+  int G, cpl;
+  ln_pick(C, &G, &cpl);
+#define LN_CALL(g, c) OPCK((ln_bwd_launch<g, c>(h, ldh, dy, dres, gamma, stats, dx, part, (int)M, C, &slabs, stream)))
+  LN_DISPATCH(G, cpl, LN_CALL, REQUIRE(false, "ln_bwd: no kernel for this row width"));
+#undef LN_CALL
+  hipLaunchKernelGGL(k_ln_colsum, dim3((2 * C + 63) / 64), dim3(256), 0, (hipStream_t)stream, (const float*)part, slabs,
+                     2 * C, dgb, 0);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// a = bf16(gelu(z)), z and a dense bf16 [R][N]
+int dca_ops_gelu_fwd(const void* z, void* a, long R, int N, void* stream) {
+  const char* e = gelu_rule(R, N);
+  REQUIRE(!e, e);
+  REQUIRE(z && a, "gelu_fwd: buffer missing");
+  REQUIRE(LN_ALIGNED(z) && LN_ALIGNED(a), e = gelu_rule(0, 0));
+  const long n8 = R * N / 8;
+  hipLaunchKernelGGL(k_gelu_fwd, dim3(grid_for(n8, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)z, (bf16_t*)a, n8);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// dz = bf16(dy gelu'(z)) and db [N] (+)= the column sums of the fp32 dz.  dy [R][N] fp32 or bf16 (dy_bf16); part:
+// nchunk * N floats
+int dca_ops_gelu_bwd(const void* dy, int dy_bf16, const void* z, void* dz, float* part, float* db, long R, int N,
+                     int nchunk, int accumulate, void* stream) {
+  const char* e = gelu_rule(R, N);
+  REQUIRE(!e, e);
+  REQUIRE(dy && z && dz && part && db && nchunk >= 1 && nchunk <= 65535, "gelu_bwd: buffer missing");
+  REQUIRE(LN_ALIGNED(dy) && LN_ALIGNED(z) && LN_ALIGNED(dz) && LN_ALIGNED(part), e = gelu_rule(0, 0));
+  const int rpb = (int)((R + nchunk - 1) / nchunk), chunks = (int)((R + rpb - 1) / rpb);
+  const dim3 g((N + 255) / 256, chunks), b(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dy_bf16)
+    hipLaunchKernelGGL((k_gelu_bwd<bf16_t>), g, b, 0, st, (const bf16_t*)dy, (const bf16_t*)z, (bf16_t*)dz, part,
+                       (int)R, N, rpb);
+  else
+    hipLaunchKernelGGL((k_gelu_bwd<float>), g, b, 0, st, (const float*)dy, (const bf16_t*)z, (bf16_t*)dz, part, (int)R,
+                       N, rpb);
+  OPCK(hipGetLastError());
+  hipLaunchKernelGGL(k_ln_colsum, dim3((N + 63) / 64), dim3(256), 0, st, (const float*)part, chunks, N, db, accumulate);
   OPCK(hipGetLastError());
   return 0;
 }

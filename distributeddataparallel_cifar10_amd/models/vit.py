@@ -3,7 +3,8 @@ class token and a learned position embedding, ``depth`` pre-LayerNorm blocks (LN
 self-attention -> proj Linear -> add; LN -> Linear -> GELU -> Linear -> add), a final LN and a Linear head on the class
 token.  No dropout.  The qkv Linear's output is split as [B, L, 3, heads, D]: the layout csrc/ops_attn.hip reads.
 
-On the ops path (``OpsModel``) every Linear runs on the MFMA GEMMs and the attention on csrc/ops_attn.hip; this
+On the ops path (``OpsModel``) every Linear runs on the MFMA GEMMs, the attention on csrc/ops_attn.hip, and the
+LayerNorms (each fused with the residual add before it) and the GELU on csrc/ops_ln.hip; this
 module's own forward is stock torch (``scaled_dot_product_attention``) and runs on the CPU.
 """
 from __future__ import annotations

@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _lock = threading.Lock()
 _lib = None
 
@@ -209,9 +209,24 @@ ATTN_ENTRY_POINTS = {
 }
 
 
+# Fused residual-add LayerNorm and GELU (csrc/ops_ln.hip), run on the GPU by tests/test_ops_ln_gpu.py.  Rows are bf16,
+# gamma / beta the fp32 master parameters, stats fp32 [M, 2] = (mean, rstd).
+LN_ENTRY_POINTS = {
+    "dca_ops_ln_rule": [c_long, c_int, c_int],  # M, C, ldx
+    # x, delta, gamma, beta, hsum, y, stats, M, C, ldx, eps, max_wg, stream
+    "dca_ops_ln_fwd": [c_void_p] * 7 + [c_long, c_int, c_int, c_float, c_int, c_void_p],
+    # h, ldh, dy, dres, gamma, stats, dx, part, dgb, M, C, slabs, stream
+    "dca_ops_ln_bwd": [c_void_p, c_int] + [c_void_p] * 7 + [c_long, c_int, c_int, c_void_p],
+    "dca_ops_gelu_rule": [c_long, c_int],  # R, N
+    "dca_ops_gelu_fwd": [c_void_p, c_void_p, c_long, c_int, c_void_p],  # z, a, R, N, stream
+    # dy, dy_bf16, z, dz, part, db, R, N, nchunk, accumulate, stream
+    "dca_ops_gelu_bwd": [c_void_p, c_int] + [c_void_p] * 4 + [c_long, c_int, c_int, c_int, c_void_p],
+}
+
+
 def _declare_later(lib):
     for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS,
-                           **DWCONV_ENTRY_POINTS, **SE_ENTRY_POINTS, **ATTN_ENTRY_POINTS}.items():
+                           **DWCONV_ENTRY_POINTS, **SE_ENTRY_POINTS, **ATTN_ENTRY_POINTS, **LN_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

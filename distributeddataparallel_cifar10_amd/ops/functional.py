@@ -229,7 +229,7 @@ def cast_bf16(x: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------------------
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, relu, out_dtype, fp8, sinks):
+    def forward(ctx, x, w, b, relu, out_dtype, fp8, sinks, gelu=False):
         xb = x.contiguous() if x.dtype == torch.bfloat16 else cast_bf16(x.float())
         wb = cast_bf16(w.detach())
         if fp8:
@@ -238,17 +238,21 @@ class _Linear(torch.autograd.Function):
             y = gemm(qx, qw, bias=b, relu=relu, out_dtype=out_dtype, amax_a=ax, amax_b=aw)
         else:
             y = gemm(xb, wb, bias=b, relu=relu, out_dtype=out_dtype)
-        ctx.save_for_backward(xb, wb, y if relu else None)
-        ctx.relu, ctx.has_b, ctx.sinks = relu, b is not None, sinks
-        return y
+        # gelu: y is the bf16 pre-activation (bias in the GEMM epilogue), kept for the backward
+        ctx.save_for_backward(xb, wb, y if relu or gelu else None)
+        ctx.relu, ctx.gelu, ctx.has_b, ctx.sinks = relu, gelu, b is not None, sinks
+        return gelu_fwd(y) if gelu else y
 
     @staticmethod
     def backward(ctx, dy):
         xb, wb, y = ctx.saved_tensors
         sw, sb = ctx.sinks if ctx.sinks is not None else (None, None)
         want_db = ctx.has_b and (ctx.needs_input_grad[2] or sb is not None)
-        # ReLU mask, bf16 operand and the bias gradient (into its flat DDP view when sunk) in one launch
-        dyb, db = dy_prep(dy, y if ctx.relu else None, want_db=want_db, db_into=sb[0] if sb is not None else None)
+        # ReLU mask or GELU derivative, bf16 operand and the bias gradient (into its flat DDP view when sunk) in one pass
+        if ctx.gelu:
+            dyb, db = gelu_bwd(dy.contiguous(), y, want_db=want_db, db_into=sb[0] if sb is not None else None)
+        else:
+            dyb, db = dy_prep(dy, y if ctx.relu else None, want_db=want_db, db_into=sb[0] if sb is not None else None)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = gemm(dyb, wb, tb=True, out_dtype=torch.bfloat16)  # dX = dY . W
@@ -263,18 +267,27 @@ class _Linear(torch.autograd.Function):
             if sink is not None:
                 sink[1]()
         ctx.sinks = None
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
-def linear(x, w, b=None, relu=False, out_dtype=torch.float32, fp8=False):
+def linear(x, w, b=None, relu=False, out_dtype=torch.float32, fp8=False, gelu=False):
     """x [B, in] -> [B, out].  Under FlatBucketDDP (grad sinks on w and b) the weight and bias gradients are written
-    straight into the flat gradient buffer by the backward's kernels (no autograd accumulate kernels)."""
+    straight into the flat gradient buffer by the backward's kernels (no autograd accumulate kernels).
+    gelu=True: returns bf16 gelu(x w^T + b) (exact erf form, csrc/ops_ln.hip): the GEMM writes the bf16 pre-activation,
+    the GELU is a kernel beside it, and its backward does ``dy_prep``'s work in the same pass (``gelu_bwd``).  It needs
+    out_dtype=torch.bfloat16 and out features % 8 == 0, and is refused together with relu or fp8."""
+    if gelu:
+        if relu or fp8:
+            raise ValueError("linear: gelu=True is not available together with relu=True or fp8=True")
+        if out_dtype != torch.bfloat16:
+            raise ValueError("linear: gelu=True returns bfloat16 (the pre-activation is kept in bf16); pass "
+                             "out_dtype=torch.bfloat16")
     sinks = None
     if torch.is_grad_enabled() and b is not None:
         sw, sb = grad_sink(w), grad_sink(b)
         if sw is not None and sb is not None and sw[0].is_contiguous():
             sinks = (sw, sb)
-    return _Linear.apply(x, w, b, relu, out_dtype, fp8, sinks)
+    return _Linear.apply(x, w, b, relu, out_dtype, fp8, sinks, gelu)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1644,6 +1657,193 @@ def attention(qkv: torch.Tensor, heads: int, scale: Optional[float] = None) -> t
     b, l, h, d = _attn_dims(qkv)
     o = _Attention.apply(qkv, float(d ** -0.5 if scale is None else scale))
     return o.view(b, l, h * d)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Fused residual-add LayerNorm and GELU (csrc/ops_ln.hip).  LayerNorm: one launch forward; the backward is the row
+# kernel (input gradient, residual join, per-workgroup parameter-gradient slabs) and a small slab sum.  The shape
+# rule lives in the launchers (dca_ops_ln_rule, device-free).
+# ------------------------------------------------------------------------------------------------------------
+_CUS = {}
+
+
+def _cu_count(dev) -> int:
+    dev = torch.device(dev)
+    if dev not in _CUS:
+        _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return _CUS[dev]
+
+
+def ln_check(m: int, c: int, ldx: int) -> None:
+    """``m`` rows of stride ``ldx`` elements of which the first ``c`` are normalised."""
+    dims = [int(m), int(c), int(ldx)]
+    if max(dims[1:]) >= 2 ** 31 or min(dims) < 0:
+        dims = [0, 0, 0]  # (no shape the rule takes)
+    if N.lib().dca_ops_ln_rule(*dims) != 0:
+        raise ValueError(f"layer_norm: (M, C, ldx) = {(m, c, ldx)}: "
+                         f"{N.lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def _ln_rows(t: torch.Tensor, name: str):
+    """(M, row stride) of ``t`` [..., C] seen as M rows of unit inner stride and one row stride (a contiguous tensor,
+    or a view such as ``h[:, 0]``)."""
+    if t.dim() < 2 or t.stride(-1) != 1:
+        raise ValueError(f"layer_norm: {name} is [..., C] with unit inner stride, got shape {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    c = t.shape[-1]
+    dims = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n != 1]
+    if any(s0 != n1 * s1 for (_, s0), (n1, s1) in zip(dims[:-1], dims[1:])):
+        raise ValueError(f"layer_norm: the rows of {name} have one stride, got shape {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    return t.numel() // max(c, 1), (dims[-1][1] if dims else c)
+
+
+def _ln_param(p, c, name) -> None:
+    if p.dtype != torch.float32 or tuple(p.shape) != (c,) or not p.is_contiguous():
+        raise ValueError(f"layer_norm: {name} is a contiguous float32 tensor of shape ({c},), "
+                         f"got {p.dtype} {tuple(p.shape)}")
+
+
+def _ln_dense(t, shape, name, dtype=torch.bfloat16) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"layer_norm: {name} is a contiguous {dtype} tensor of shape {tuple(shape)}, "
+                         f"got {t.dtype} {tuple(t.shape)}")
+
+
+def layer_norm_fwd(x, delta, weight, bias, eps=1e-5, max_wg=None):
+    """(hsum, y, stats): hsum = bf16(x + delta) (None without ``delta``), y = LayerNorm(hsum) * weight + bias over the
+    last dimension (bf16, contiguous, x's shape), stats fp32 [M, 2] = (mean, rstd) of the rounded hsum.  x / delta: bf16
+    [..., C] with one row stride; weight / bias: the fp32 parameters.  ``max_wg``: the most workgroups (default 8 per
+    compute unit)."""
+    _dev_check(x, delta, weight, bias)
+    m, ldx = _ln_rows(x, "x")
+    c = x.shape[-1]
+    if delta is not None and (delta.dtype != x.dtype or delta.shape != x.shape or _ln_rows(delta, "residual")[1] != ldx):
+        raise ValueError(f"layer_norm: residual has x's dtype, shape and row stride ({x.dtype} {tuple(x.shape)} {ldx}), "
+                         f"got {delta.dtype} {tuple(delta.shape)} strides {delta.stride()}")
+    _ln_param(weight, c, "weight"), _ln_param(bias, c, "bias")
+    ln_check(m, c, ldx)
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    hsum = torch.empty_like(y) if delta is not None else None
+    stats = torch.empty(m, 2, dtype=torch.float32, device=x.device)
+    N.check(N.lib().dca_ops_ln_fwd(N.ptr(x), N.ptr(delta), N.ptr(weight), N.ptr(bias), N.ptr(hsum), N.ptr(y),
+                                   N.ptr(stats), m, c, ldx, float(eps),
+                                   int(max_wg) if max_wg else 8 * _cu_count(x.device), N.stream(x.device)), "ln_fwd")
+    return hsum, y, stats
+
+
+def layer_norm_bwd(h, dy, dres, weight, stats, slabs=None):
+    """(dx, dgamma, dbeta) from the forward's normalised input ``h`` (hsum, or x when there was no residual; one row
+    stride), its stats, dy and the optional skip-path gradient ``dres`` (bf16, contiguous, h's shape): dx =
+    LayerNorm'(dy) + dres in bf16 (contiguous), dgamma / dbeta fp32 [C].  ``slabs``: the most workgroups, each of
+    which writes one partial row of the parameter gradients (default 4 per compute unit)."""
+    _dev_check(h, dy, dres, weight, stats)
+    m, ldh = _ln_rows(h, "h")
+    c = h.shape[-1]
+    _ln_dense(dy, h.shape, "dy")
+    if dres is not None:
+        _ln_dense(dres, h.shape, "dres")
+    _ln_param(weight, c, "weight")
+    _ln_dense(stats, (m, 2), "stats", torch.float32)
+    ln_check(m, c, ldh)
+    slabs = max(1, min(int(slabs) if slabs else 4 * _cu_count(h.device), m))
+    dx = torch.empty(h.shape, dtype=torch.bfloat16, device=h.device)
+    part = torch.empty(slabs, 2, c, dtype=torch.float32, device=h.device)
+    dgb = torch.empty(2, c, dtype=torch.float32, device=h.device)
+    N.check(N.lib().dca_ops_ln_bwd(N.ptr(h), ldh, N.ptr(dy), N.ptr(dres), N.ptr(weight), N.ptr(stats), N.ptr(dx),
+                                   N.ptr(part), N.ptr(dgb), m, c, slabs, N.stream(h.device)), "ln_bwd")
+    return dx, dgb[0], dgb[1]
+
+
+class _LayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, residual):
+        hsum, y, stats = layer_norm_fwd(x, residual, weight.detach(), bias.detach(), eps)
+        ctx.save_for_backward(x if hsum is None else hsum, weight, stats)  # (under no_grad autograd keeps none of them)
+        ctx.set_materialize_grads(False)
+        return y if hsum is None else (hsum, y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        h, weight, stats = ctx.saved_tensors
+        dres, dy = (None, grads[0]) if len(grads) == 1 else grads
+        if dres is not None:
+            dres = dres.to(torch.bfloat16).contiguous()
+        if dy is None:  # only hsum was used: the skip path's gradient passes through
+            return dres, None, None, None, dres
+        dx, dgamma, dbeta = layer_norm_bwd(h, dy.to(torch.bfloat16).contiguous(), dres, weight.detach(), stats)
+        return dx, dgamma, dbeta, None, (dx if len(grads) == 2 else None)
+
+
+def layer_norm(x, weight, bias, eps: float = 1e-5, residual=None):
+    """LayerNorm over the last dimension of ``x`` [..., C] (bf16, CUDA, unit inner stride and one row stride: contiguous
+    or a view such as ``h[:, 0]``), optionally fused with the residual add that feeds it: without ``residual`` returns
+    y = LN(x) * weight + bias; with it returns (hsum, y), hsum = bf16(x + residual) and y = LN(hsum) * weight + bias.
+    weight / bias: the fp32 parameters [C], C % 8 == 0, 64 <= C <= 2048.  Outputs are contiguous bf16.  The backward
+    adds hsum's gradient (the skip path) to the LayerNorm's input gradient in the same pass and hands that one tensor
+    to both ``x`` and ``residual``; the parameter gradients are fp32."""
+    for t, name in ((x, "x"), (residual, "residual")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16):
+            raise TypeError(f"layer_norm: {name} is a bfloat16 tensor, got {getattr(t, 'dtype', type(t))}")
+    _dev_check(x, residual, weight, bias)
+    return _LayerNorm.apply(x, weight, bias, float(eps), residual)
+
+
+def _gelu_operand(t, name, shape=None, dtypes=(torch.bfloat16,)):
+    if t.dtype not in dtypes or t.dim() < 1 or not t.is_contiguous() or (shape is not None and t.shape != shape):
+        raise ValueError(f"gelu: {name} is a contiguous tensor of {' or '.join(str(d) for d in dtypes)}"
+                         f"{'' if shape is None else ' of shape ' + str(tuple(shape))}, got {t.dtype} {tuple(t.shape)}")
+    r, n = t.numel() // max(t.shape[-1], 1), t.shape[-1]
+    if N.lib().dca_ops_gelu_rule(r, n) != 0:
+        raise ValueError(f"gelu: {name} {tuple(t.shape)}: {N.lib().dca_ops_last_error().decode(errors='replace')}")
+    return r, n
+
+
+def gelu_fwd(z):
+    """bf16(gelu(z)), exact erf form, for a contiguous bf16 [..., N], N % 8 == 0."""
+    _dev_check(z)
+    r, n = _gelu_operand(z, "z")
+    a = torch.empty_like(z)
+    N.check(N.lib().dca_ops_gelu_fwd(N.ptr(z), N.ptr(a), r, n, N.stream(z.device)), "gelu_fwd")
+    return a
+
+
+def gelu_bwd(dy, z, want_db: bool = True, db_into: Optional[torch.Tensor] = None):
+    """``dy_prep`` for a GELU layer, one pass over dy [..., N] (fp32 / bf16) and the saved pre-activation z (bf16):
+    (dz = dy * gelu'(z) as the bf16 GEMM operand, db = the column sums of the unrounded fp32 dz, or None).
+    db_into: accumulate the column sums into this fp32 view instead (a flat DDP gradient sink)."""
+    _dev_check(dy, z, db_into)
+    r, n = _gelu_operand(z, "z")
+    _gelu_operand(dy, "dy", z.shape, (torch.bfloat16, torch.float32))
+    dz = torch.empty_like(z)
+    db = db_into if db_into is not None else torch.empty(n, dtype=torch.float32, device=z.device)
+    ncb = (n + 255) // 256  # 256-column blocks
+    nchunk = max(1, min((1024 + ncb - 1) // ncb, (r + 15) // 16))  # ~1024 workgroups, >= 16 rows each
+    part = torch.empty(nchunk * n, dtype=torch.float32, device=z.device)
+    N.check(N.lib().dca_ops_gelu_bwd(N.ptr(dy), int(dy.dtype == torch.bfloat16), N.ptr(z), N.ptr(dz), N.ptr(part),
+                                     N.ptr(db), r, n, nchunk, int(db_into is not None), N.stream(z.device)), "gelu_bwd")
+    return dz, (db if want_db and db_into is None else None)
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z):
+        ctx.save_for_backward(z)
+        return gelu_fwd(z)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, da):
+        return gelu_bwd(da.contiguous(), ctx.saved_tensors[0], want_db=False)[0]
+
+
+def gelu(z: torch.Tensor) -> torch.Tensor:
+    """GELU (exact erf form) of a contiguous bf16 CUDA tensor [..., N], N % 8 == 0, on csrc/ops_ln.hip."""
+    if not isinstance(z, torch.Tensor) or z.dtype != torch.bfloat16:
+        raise TypeError(f"gelu: z is a bfloat16 tensor, got {getattr(z, 'dtype', type(z))}")
+    _dev_check(z)
+    return _Gelu.apply(z)
 
 
 # ------------------------------------------------------------------------------------------------------------

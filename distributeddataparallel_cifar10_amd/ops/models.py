@@ -27,9 +27,12 @@ switches to channels-last bf16 once, and runs:
 * VisionTransformer: the patch embedding as a reshape of the input into [B L', 3 p p] rows and ``linear`` on the conv
   weight viewed as a matrix, then per block qkv ``linear`` -> ``attention`` (csrc/ops_attn.hip, directly on the qkv
   linear's [B, L, 3 H 64] output) -> proj ``linear``, and the MLP's two ``linear``s; bf16 between layers, fp32 logits.
-  Stated scope: LayerNorm, GELU, the residual adds and the position-embedding add are torch operations on bf16
-  tensors (as ``DCA_OPS_ROI=0`` also mixes torch autograd with ops functions); bf16 only.  A head width or sequence
-  length outside the attention rule raises the rule's ``ValueError`` at the first forward.
+  Each residual add is fused into the LayerNorm that follows it and fc1's GELU runs beside its GEMM (``layer_norm``,
+  ``linear(gelu=True)``: csrc/ops_ln.hip); the last block's fc2 output is joined and normalised on the class-token
+  rows only.  The class-token concat and the position-embedding add are the only torch operations left on the
+  activations; bf16 only.  ``DCA_OPS_LN=0`` keeps LayerNorm, GELU and the adds on torch (A/B comparisons).  A head
+  width or sequence length outside the attention rule, or a width outside the LayerNorm rule, raises the rule's
+  ``ValueError`` at the first forward.
 """
 from __future__ import annotations
 
@@ -43,6 +46,9 @@ from . import functional as F
 # DCA_OPS_MASKED_JOIN=0: bn3's backward writes the identity gradient dout * mask as before (A/B comparisons)
 _MASKED_JOIN = os.environ.get("DCA_OPS_MASKED_JOIN", "1") != "0"
 _RES_LINK = os.environ.get("DCA_OPS_RES_LINK", "1") != "0"  # downsample blocks: the residual gradient over a link
+# DCA_OPS_LN=0: the ViT's LayerNorm, GELU and residual adds run as torch operations on bf16 tensors as before (A/B
+# comparisons); read by ``OpsModel._vit`` at every forward
+OPS_LN = os.environ.get("DCA_OPS_LN", "1") != "0"
 
 
 def _is_netresdeep(m: nn.Module) -> bool:
@@ -246,8 +252,44 @@ class OpsModel(nn.Module):
         return self.head(h, m.fc)
 
     def _vit(self, x):
-        """models/vit.py on ``linear`` and ``attention``; LayerNorm, GELU and the adds are torch operations on bf16
-        tensors (the module docstring's stated scope)."""
+        """models/vit.py on ``linear``, ``attention`` and ``layer_norm``.  Every residual add is fused into the
+        LayerNorm that follows it (``layer_norm(h, ..., residual=...)`` returns the new stream and its normalised form;
+        its backward joins the skip-path gradient), fc1 runs ``linear(gelu=True)``, and the last block's fc2 output is
+        joined and normalised on the class-token rows only.  The class-token concat and the position-embedding add stay
+        torch operations on bf16 tensors.  ``OPS_LN`` False: ``_vit_torch``."""
+        if not OPS_LN:
+            return self._vit_torch(x)
+        m, bf = self.module, torch.bfloat16
+
+        def lin(h, layer, out_dtype=bf, gelu=False):
+            return F.linear(h, layer.weight, layer.bias, out_dtype=out_dtype, gelu=gelu)
+
+        def norm(h, ln, residual=None):
+            return F.layer_norm(h, ln.weight, ln.bias, ln.eps, residual=residual)
+
+        n, c, hh, ww = x.shape
+        p, dim = m.patch, m.dim
+        rows = x.reshape(n, c, hh // p, p, ww // p, p).permute(0, 2, 4, 1, 3, 5).reshape(-1, c * p * p).to(bf)
+        tok = F.linear(rows, m.patch_embed.weight.reshape(dim, -1), m.patch_embed.bias, out_dtype=bf)
+        h = torch.cat([m.cls_token.to(bf).expand(n, -1, -1), tok.view(n, -1, dim)], dim=1) + m.pos_embed.to(bf)
+        seq, blocks = h.shape[1], list(m.blocks)
+        if not blocks:
+            return lin(norm(h[:, 0], m.norm), m.head, out_dtype=torch.float32)
+        y = norm(h, blocks[0].norm1)
+        for i, b in enumerate(blocks):
+            qkv = lin(y.view(n * seq, dim), b.qkv)
+            a = F.attention(qkv.view(n, seq, 3 * dim), b.heads)
+            h, y = norm(h, b.norm2, lin(a.view(n * seq, dim), b.proj).view(n, seq, dim))
+            f = lin(lin(y.view(n * seq, dim), b.fc1, gelu=True), b.fc2).view(n, seq, dim)
+            if i + 1 < len(blocks):
+                h, y = norm(h, blocks[i + 1].norm1, f)
+            else:  # only the class token reaches the head
+                _, y = norm(h[:, 0], m.norm, f[:, 0])
+        return lin(y, m.head, out_dtype=torch.float32)
+
+    def _vit_torch(self, x):
+        """``_vit`` with LayerNorm, GELU and the residual adds as torch operations on bf16 tensors (DCA_OPS_LN=0: A/B
+        comparisons)."""
         m, bf = self.module, torch.bfloat16
         tnf = torch.nn.functional
 

@@ -194,6 +194,7 @@ using namespace dca::ops;
 #include "ops_roi.hip"
 #include "ops_gconv.hip"
 #include "ops_dwconv.hip"
+#include "ops_dwconv7.hip"
 #include "ops_se.hip"
 #include "ops_attn.hip"
 #include "ops_ln.hip"
@@ -206,7 +207,7 @@ std::atomic<bool> g_lds_raised{false};    // the table's dynamic-LDS limits are 
 extern "C" {
 
 const char* dca_ops_last_error() { return g_err.c_str(); }
-int dca_ops_abi_version() { return 22; }
+int dca_ops_abi_version() { return 23; }
 
 // The BN rule alone, callable with no device: the kernels dca_ops_bn_fwd / _fwd_parts / _eval / _bwd launch for M rows
 // of C channels in this fused form (has_mask: a ReLU bit mask is stored / read; raff: on-the-fly residual BN); -1
@@ -1006,6 +1007,86 @@ int dca_ops_dwconv_wgrad(const void* x, const void* dy, float* ws, int slabs, fl
   OPCK(hipGetLastError());
   hipLaunchKernelGGL(k_dwconv_wgrad_reduce, dim3((C * 9 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const float*)ws, dw, C, used, beta);
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Depthwise 7 x 7 convolution (ops_dwconv7.hip).  x / y / dy / dx: dense NHWC bf16 [N][H][W][C]; w / dw: the fp32 master
+// weight [C][1][7][7], read directly (rounded to bf16 in the kernels): there is no packed operand; bias / db: fp32 [C].
+static const char* dwconv7_rule(int N, int H, int W, int Cin, int Cout, int groups, int KH, int KW, int stride, int pad) {
+  static const char* rule =
+      "dwconv7: the depthwise 7x7 convolution rule is 7x7, pad 3, stride 1, Cin == Cout == groups == C, C % 8 == 0, "
+      "rows of 1 to 64 pixels, fewer than 2^31 elements (32-bit byte offsets) and 16-byte aligned activations";
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0) return rule;
+  if (KH != 7 || KW != 7 || pad != 3 || stride != 1) return rule;
+  if (Cin != Cout || Cin != groups || Cin % 8) return rule;
+  if (W > 64) return rule;
+  if ((long)N * H * W * Cin >= (1L << 31)) return rule;
+  return nullptr;
+}
+int dca_ops_dwconv7_rule(int N, int H, int W, int Cin, int Cout, int groups, int KH, int KW, int stride, int pad) {
+  const char* e = dwconv7_rule(N, H, W, Cin, Cout, groups, KH, KW, stride, pad);
+  REQUIRE(!e, e);
+  return 0;
+}
+// The work split (ops_dwconv7.hip, D7Plan): log2 of the channel pairs per slab, the widest whose 256 / CP columns
+// cover the row and no wider than the channels; and the strips per image: whole images when they give about 768 units
+// (three workgroups on each of 256 CUs), else strips of at least 8 rows.
+static D7Geom dwconv7_geom(int N, int H, int W, int C, int* lp) {
+  *lp = W > 32 ? 2 : W > 16 ? 3 : W > 8 ? 4 : 5;
+  while (*lp > 2 && (2 << *lp) > C) --*lp;
+  const long units = (long)N * ((C + (2 << *lp) - 1) / (2 << *lp));
+  const int strips = (int)std::max(1L, std::min((768 + units - 1) / units, (long)std::max(1, H / 8)));
+  return D7Geom{N, H, W, C, strips};
+}
+#define D7_LP_SWITCH(lp, M) \
+  do {                      \
+    if (lp == 5) M(5);      \
+    else if (lp == 4) M(4); \
+    else if (lp == 3) M(3); \
+    else M(2);              \
+  } while (0)
+
+// Forward y = bf16(conv(x) + bias) (bias or null); flip 1: the input gradient (x = dy, y = dx, bias null).
+int dca_ops_dwconv7_fwd(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int C, int flip,
+                        void* stream) {
+  const char* e = dwconv7_rule(N, H, W, C, C, C, 7, 7, 1, 3);
+  REQUIRE(!e, e);
+  REQUIRE(x && w && y && (flip == 0 || (flip == 1 && !bias)), "dwconv7_fwd: buffer missing, or flip with a bias");
+  REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0, "dwconv7_fwd: misaligned buffer");
+  int lp;
+  const D7Geom g = dwconv7_geom(N, H, W, C, &lp);
+  // about 1536 workgroups in all: each reads its 98 weights once and then walks two or more units
+  const int nslab = (C + (2 << lp) - 1) / (2 << lp), wgs = std::min(N * g.strips, std::max(1, 1536 / nslab));
+  const dim3 grid((unsigned)wgs * nslab);
+#define D7_FWD(LP)                                                                                              \
+  hipLaunchKernelGGL((k_dwconv7x7_fwd<LP>), grid, dim3(DW_NT), 0, (hipStream_t)stream, (const bf16_t*)x, w, bias, \
+                     (bf16_t*)y, g, flip)
+  D7_LP_SWITCH(lp, D7_FWD);
+#undef D7_FWD
+  OPCK(hipGetLastError());
+  return 0;
+}
+
+// Weight gradient dw [C][1][7][7] and bias gradient db [C] (or null), fp32 (beta 1: accumulated into both).  ws:
+// slabs * C * 50 floats; slabs (>= 1) bounds the workgroups per channel slab.
+int dca_ops_dwconv7_wgrad(const void* x, const void* dy, float* ws, int slabs, float* dw, float* db, int beta, int N,
+                          int H, int W, int C, void* stream) {
+  const char* e = dwconv7_rule(N, H, W, C, C, C, 7, 7, 1, 3);
+  REQUIRE(!e, e);
+  REQUIRE(x && dy && ws && dw && slabs >= 1 && (beta == 0 || beta == 1), "dwconv7_wgrad: buffer missing, slabs < 1 or beta");
+  REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0, "dwconv7_wgrad: misaligned buffer");
+  int lp;
+  const D7Geom g = dwconv7_geom(N, H, W, C, &lp);
+  const int nslab = (C + (2 << lp) - 1) / (2 << lp), used = std::min(N * g.strips, slabs);
+  const dim3 grid((unsigned)used * nslab);
+#define D7_WG(LP) \
+  hipLaunchKernelGGL((k_dwconv7x7_wgrad<LP>), grid, dim3(DW_NT), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy, ws, g)
+  D7_LP_SWITCH(lp, D7_WG);
+#undef D7_WG
+  OPCK(hipGetLastError());
+  hipLaunchKernelGGL(k_dwconv7_wgrad_reduce, dim3((C * D7_WS + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)ws, dw, db, C, used, beta);
   OPCK(hipGetLastError());
   return 0;
 }

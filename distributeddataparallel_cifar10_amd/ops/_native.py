@@ -13,7 +13,7 @@ import torch
 
 from .. import build as _build
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 _lock = threading.Lock()
 _lib = None
 
@@ -184,6 +184,17 @@ DWCONV_ENTRY_POINTS = {
 }
 
 
+# Depthwise 7x7 convolution (csrc/ops_dwconv7.hip), run on the GPU by tests/test_ops_dwconv7_gpu.py.  w / dw: the fp32
+# master weight [C, 1, 7, 7] (there is no packed operand); bias / db: fp32 [C] or null.
+DWCONV7_ENTRY_POINTS = {
+    "dca_ops_dwconv7_rule": [c_int] * 10,  # N, H, W, Cin, Cout, groups, KH, KW, stride, pad
+    # x, w, bias, y, N, H, W, C, flip, stream (flip 1: the input gradient, x = dy, y = dx, no bias)
+    "dca_ops_dwconv7_fwd": [c_void_p] * 4 + [c_int] * 5 + [c_void_p],
+    # x, dy, ws, slabs, dw, db, beta, N, H, W, C, stream
+    "dca_ops_dwconv7_wgrad": [c_void_p] * 3 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+}
+
+
 # Squeeze-and-excitation (csrc/ops_se.hip), run on the GPU by tests/test_ops_se_gpu.py.  z / dz: fp32 [N, C] gate logits.
 SE_ENTRY_POINTS = {
     "dca_ops_se_rule": [c_int] * 4,  # N, H, W, C
@@ -226,7 +237,7 @@ LN_ENTRY_POINTS = {
 
 def _declare_later(lib):
     for name, argtypes in {**LATER_ENTRY_POINTS, **ROI_ENTRY_POINTS, **GCONV_ENTRY_POINTS,
-                           **DWCONV_ENTRY_POINTS, **SE_ENTRY_POINTS, **ATTN_ENTRY_POINTS, **LN_ENTRY_POINTS}.items():
+                           **DWCONV_ENTRY_POINTS, **DWCONV7_ENTRY_POINTS, **SE_ENTRY_POINTS, **ATTN_ENTRY_POINTS, **LN_ENTRY_POINTS}.items():
         getattr(lib, name).argtypes = argtypes
     return lib
 

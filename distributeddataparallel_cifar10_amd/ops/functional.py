@@ -500,6 +500,84 @@ def dwconv_wgrad(x, dy, stride, out=None, slabs=None):
     return dw
 
 
+# ------------------------------------------------------------------------------------------------------------
+# Depthwise 7x7 convolution (csrc/ops_dwconv7.hip): groups == Cin with a weight [C, 1, 7, 7], pad 3, stride 1, with an
+# optional bias (ConvNeXt's).  Its own rule (dca_ops_dwconv7_rule, device-free).  The kernels read the fp32 master
+# weight and bias directly, so there is no packed operand; they fuse no ReLU.
+# ------------------------------------------------------------------------------------------------------------
+def _is_depthwise7(cin, wshape, groups) -> bool:
+    return _is_depthwise(cin, wshape, groups) and tuple(int(v) for v in wshape[2:]) == (7, 7)
+
+
+def dwconv7_check(xshape, wshape, stride, pad, groups) -> None:
+    n, h, wd, c = (int(v) for v in xshape)
+    co, ci, kh, kw = (int(v) for v in wshape)
+    if min(n, h, wd, c, co, ci, kh, kw) <= 0 or max(n, h, wd, c, co, kh, kw, groups) >= 2 ** 31 or ci != 1:
+        c = -1  # (no shape the rule takes)
+    if N.lib().dca_ops_dwconv7_rule(n, h, wd, c, co, int(groups), kh, kw, int(stride), int(pad)) != 0:
+        raise ValueError(f"conv: depthwise (groups={groups}) with input {tuple(xshape)}, weight {tuple(wshape)}, "
+                         f"stride {stride}, pad {pad}: {N.lib().dca_ops_last_error().decode(errors='replace')}")
+
+
+def dwconv7_entry(groups: int) -> dict:
+    """The WeightPack entry of a depthwise 7x7 conv: its groups and nothing to pack."""
+    return dict(dwconv_entry(groups), depthwise7=True)
+
+
+def _dwconv7_operands(x, w, c, bias=None) -> None:
+    _gconv_operand(x, tuple(x.shape), "x")
+    if w is not None and (w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (c, 1, 7, 7)):
+        raise ValueError(f"dwconv7: the weight is a contiguous fp32 {(c, 1, 7, 7)}, got {w.dtype} {tuple(w.shape)}")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or tuple(bias.shape) != (c,)):
+        raise ValueError(f"dwconv7: the bias is a contiguous fp32 {(c,)}, got {bias.dtype} {tuple(bias.shape)}")
+
+
+def dwconv7_fwd(x, w, bias=None, flip=False):
+    """y [N, H, W, C] bf16 = depthwise 7x7 (pad 3, stride 1) of NHWC bf16 x with the fp32 master weight w [C, 1, 7, 7],
+    plus the fp32 bias [C] when given.  flip: the taps reversed (the input gradient; no bias)."""
+    n, h, wd, c = x.shape
+    dwconv7_check(x.shape, w.shape, 1, 3, c)
+    _dev_check(x, w, bias)
+    _dwconv7_operands(x, w, c, bias)
+    if flip and bias is not None:
+        raise ValueError("dwconv7: the flipped form (the input gradient) takes no bias")
+    y = torch.empty_like(x)
+    N.check(N.lib().dca_ops_dwconv7_fwd(N.ptr(x), N.ptr(w), N.ptr(bias), N.ptr(y), n, h, wd, c, int(bool(flip)),
+                                        N.stream(x.device)), "dwconv7_fwd")
+    return y
+
+
+def dwconv7_dgrad(dy, w):
+    """dx [N, H, W, C] bf16 from dy (bf16, contiguous, the same shape) and the fp32 master weight: the forward kernel
+    with the taps flipped."""
+    return dwconv7_fwd(dy, w, flip=True)
+
+
+def dwconv7_wgrad(x, dy, out=None, slabs=None, want_db=True):
+    """(dw [C, 1, 7, 7], db [C] or None) fp32 from x and dy [N, H, W, C] (bf16, contiguous).  ``out`` = (dw, db) or
+    (dw, None): accumulate into these contiguous fp32 views instead.  Partial slabs are summed in a fixed order (no
+    atomics)."""
+    n, h, wd, c = x.shape
+    dwconv7_check(x.shape, (c, 1, 7, 7), 1, 3, c)
+    dw, db = out if out is not None else (None, None)
+    _dev_check(x, dy, dw, db)
+    _dwconv7_operands(x, None, c)
+    _gconv_operand(dy, tuple(x.shape), "dy")
+    slabs = int(slabs or max(32, min(256, 49152 // c)))
+    if slabs < 1:
+        raise ValueError("dwconv7_wgrad: at least one slab")
+    ws = torch.empty(slabs * c * 50, dtype=torch.float32, device=x.device)
+    if out is None:
+        dw = torch.empty(c, 1, 7, 7, dtype=torch.float32, device=x.device)
+        db = torch.empty(c, dtype=torch.float32, device=x.device) if want_db else None
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() != c * 49 or \
+            (db is not None and (db.dtype != torch.float32 or not db.is_contiguous() or db.numel() != c)):
+        raise ValueError("dwconv7_wgrad: the gradients go to contiguous fp32 [C, 1, 7, 7] and [C]")
+    N.check(N.lib().dca_ops_dwconv7_wgrad(N.ptr(x), N.ptr(dy), N.ptr(ws), slabs, N.ptr(dw), N.ptr(db),
+                                          int(out is not None), n, h, wd, c, N.stream(x.device)), "dwconv7_wgrad")
+    return dw, db
+
+
 class WeightPack:
     """The bf16 (and fp8) GEMM operands of every convolution of a model, rebuilt from the fp32 master weights
     by ONE kernel launch per step (``pack()``; csrc/ops_nn.hip k_pack_weights / k_pack_fp8) instead of a
@@ -524,7 +602,8 @@ class WeightPack:
         for c in self.convs:
             co, ci, kh, kw = c.weight.shape
             if _is_depthwise(c.in_channels, c.weight.shape, c.groups):  # reads the master weight: nothing to pack
-                self.entries[id(c)] = dwconv_entry(c.groups)
+                self.entries[id(c)] = (dwconv7_entry if _is_depthwise7(c.in_channels, c.weight.shape, c.groups)
+                                       else dwconv_entry)(c.groups)
                 continue
             if c.groups > 1:  # grouped: its own operands and one k_gconv_pack launch per step (pack())
                 self.entries[id(c)] = gconv_entry(c.weight, c.groups)
@@ -975,6 +1054,13 @@ class _Conv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, pad, relu, fp8, groups=1):
         packed = None
+        if _is_depthwise7(x.shape[-1], w.shape, groups):  # csrc/ops_dwconv7.hip: its own rule, a bias, no ReLU
+            dwconv7_check(x.shape, w.shape, stride, pad, groups)
+            if relu or fp8:
+                raise ValueError("conv2d: the depthwise 7x7 kernels fuse no ReLU and have no fp8 form")
+            ctx.st = dict(dw7=(x.contiguous(), w.detach()))
+            ctx.relu, ctx.has_b = False, b is not None
+            return dwconv7_fwd(ctx.st["dw7"][0], ctx.st["dw7"][1], None if b is None else b.detach().contiguous())
         if _is_depthwise(x.shape[-1], w.shape, groups):  # the depthwise rule (device-free); nothing to pack
             dwconv_check(x.shape, w.shape, stride, pad, groups)
             if b is not None or relu:
@@ -994,6 +1080,12 @@ class _Conv2d(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        if "dw7" in ctx.st:  # depthwise 7x7: dx from the flipped forward; dw and db from one pass over x and dy
+            (x, w), ctx.st = ctx.st["dw7"], None
+            dy = dy.to(torch.bfloat16).contiguous()
+            dx = dwconv7_dgrad(dy, w) if ctx.needs_input_grad[0] else None
+            dw, db = dwconv7_wgrad(x, dy, want_db=ctx.has_b) if ctx.needs_input_grad[1] or ctx.has_b else (None, None)
+            return dx, dw, db, None, None, None, None, None
         (y,) = ctx.saved_tensors
         db = None
         if ctx.relu or (ctx.has_b and ctx.needs_input_grad[2]):  # ReLU mask + bias gradient: one launch
@@ -1202,7 +1294,8 @@ def conv2d(x, w, b=None, stride=1, pad=0, relu=False, fp8=False, groups=1):
     """x: [N, H, W, Cin] bf16 (NHWC); w: [Cout, Cin / groups, KH, KW] fp32 -> [N, Ho, Wo, Cout] bf16.  groups > 1: the
     grouped 3x3 kernels (groups == Cin with a [C, 1, 3, 3] weight: the depthwise ones), for the shapes their rule takes
     (``gconv_ok`` / ``dca_ops_dwconv_rule``; a ValueError states the rule otherwise), without bias,
-    ReLU or fp8."""
+    ReLU or fp8.  groups == Cin with a [C, 1, 7, 7] weight, pad 3, stride 1: the depthwise 7x7 kernels
+    (``dca_ops_dwconv7_rule``), with an optional bias, without ReLU or fp8."""
     return _Conv2d.apply(x, w, b, stride, pad, relu, fp8, groups)
 
 

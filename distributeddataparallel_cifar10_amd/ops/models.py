@@ -33,6 +33,10 @@ switches to channels-last bf16 once, and runs:
   activations; bf16 only.  ``DCA_OPS_LN=0`` keeps LayerNorm, GELU and the adds on torch (A/B comparisons).  A head
   width or sequence length outside the attention rule, or a width outside the LayerNorm rule, raises the rule's
   ``ValueError`` at the first forward.
+* ConvNeXt (``models/convnext.py``): NHWC bf16 between layers; the stem and the 2x2 downsample convs as patchify GEMMs,
+  per block the depthwise 7x7 with bias (csrc/ops_dwconv7.hip) -> ``layer_norm`` over the [N H W, C] rows ->
+  ``linear(gelu=True)`` -> ``linear``; the layer-scale multiply and the residual add stay torch operations on bf16;
+  global average pool -> ``layer_norm`` -> ``linear`` (fp32 logits).  bf16 only.
 """
 from __future__ import annotations
 
@@ -64,6 +68,11 @@ def _is_vit(m: nn.Module) -> bool:
     return all(hasattr(m, a) for a in ("patch_embed", "cls_token", "pos_embed", "blocks", "norm", "head"))
 
 
+def _is_convnext(m: nn.Module) -> bool:
+    return (all(hasattr(m, a) for a in ("stem", "downsamples", "stages", "norm", "head")) and len(m.stages) > 0
+            and all(hasattr(b, "dwconv") and hasattr(b, "gamma") for s in m.stages for b in s))
+
+
 class OpsModel(nn.Module):
     def __init__(self, model: nn.Module, fp8: bool = False):
         super().__init__()
@@ -74,6 +83,10 @@ class OpsModel(nn.Module):
             self.kind = "vit"
             if fp8:
                 raise ValueError("OpsModel: fp8 is not available for a vision transformer (its layers run bf16)")
+        if _is_convnext(model):
+            self.kind = "convnext"
+            if fp8:
+                raise ValueError("OpsModel: fp8 is not available for a ConvNeXt (its layers run bf16)")
         if fp8 and any(getattr(m, "se", None) is not None for m in model.modules()):
             raise ValueError("OpsModel: fp8 is not available for a squeeze-and-excitation model (its blocks run bf16)")
         self._pack = None
@@ -87,6 +100,8 @@ class OpsModel(nn.Module):
             return self._mobilenet(self.begin(x))
         if self.kind == "vit":
             return self._vit(x)
+        if self.kind == "convnext":
+            return self._convnext(x)
         return self._resnet(self.begin(x))
 
     def begin(self, x: torch.Tensor) -> torch.Tensor:
@@ -286,6 +301,41 @@ class OpsModel(nn.Module):
             else:  # only the class token reaches the head
                 _, y = norm(h[:, 0], m.norm, f[:, 0])
         return lin(y, m.head, out_dtype=torch.float32)
+
+    def _convnext(self, x):
+        """models/convnext.py on NHWC bf16: the stem and the 2x2 downsample convs as patchify GEMMs (the input cut into
+        [rows, patch pixels x channels] and ``linear`` on the conv weight viewed as a matrix, as the ViT's patch
+        embedding), the depthwise 7x7 with its bias on csrc/ops_dwconv7.hip, every LayerNorm as ``layer_norm`` over the
+        [N H W, C] rows, the MLP as ``linear(gelu=True)`` and ``linear``.  The layer-scale multiply and the block's
+        residual add stay torch operations on bf16 tensors."""
+        m, bf = self.module, torch.bfloat16
+
+        def lin(h, layer, out_dtype=bf, gelu=False):
+            return F.linear(h, layer.weight, layer.bias, out_dtype=out_dtype, gelu=gelu)
+
+        def norm(h, ln):
+            return F.layer_norm(h, ln.weight, ln.bias, ln.eps)
+
+        n, c, hh, ww = x.shape
+        p, conv = m.patch, m.stem[0]
+        hh, ww = hh // p, ww // p
+        rows = x.reshape(n, c, hh, p, ww, p).permute(0, 2, 4, 1, 3, 5).reshape(-1, c * p * p).to(bf)
+        h = F.linear(rows, conv.weight.reshape(conv.out_channels, -1), conv.bias, out_dtype=bf)
+        h = norm(h, m.stem[1]).view(n, hh, ww, -1)
+        for i, stage in enumerate(m.stages):
+            if i:  # LayerNorm, then the 2x2 / 2 conv over rows of (kh, kw, c)
+                ln, conv = m.downsamples[i - 1]
+                c, hh, ww = h.shape[-1], hh // 2, ww // 2
+                rows = norm(h.view(-1, c), ln).view(n, hh, 2, ww, 2, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, 4 * c)
+                wm = conv.weight.permute(0, 2, 3, 1).reshape(conv.out_channels, -1)
+                h = F.linear(rows, wm, conv.bias, out_dtype=bf).view(n, hh, ww, -1)
+            c = h.shape[-1]
+            for b in stage:
+                y = F.conv2d(h, b.dwconv.weight, b.dwconv.bias, stride=1, pad=3, groups=c)
+                y = lin(lin(norm(y.view(-1, c), b.norm), b.pwconv1, gelu=True), b.pwconv2)
+                h = h + (b.gamma.to(bf) * y).view_as(h)
+        feat = F.global_avg_pool(h, out_dtype=bf)
+        return lin(norm(feat, m.norm), m.head, out_dtype=torch.float32)
 
     def _vit_torch(self, x):
         """``_vit`` with LayerNorm, GELU and the residual adds as torch operations on bf16 tensors (DCA_OPS_LN=0: A/B

@@ -69,7 +69,7 @@ class TrainConfig:
     backend: str = "nccl"
     port: Optional[int] = None
     timeout_s: Optional[float] = None
-    # netresdeep | resnet50 | resnext50 | seresnet50 | seresnext50 | mobilenet | vit (all but the first: the generic path)
+    # netresdeep | resnet50 | resnext50 | seresnet50 | seresnext50 | mobilenet | vit | convnext (all but the first: the generic path)
     model: str = "netresdeep"
     bucket_mb: float = 4.0           # FlatBucketDDP bucket cap (generic path)
     profile: Optional[str] = None    # directory for torch.profiler traces / kernel summary
@@ -136,7 +136,7 @@ def add_cli_args(ap: argparse.ArgumentParser, batch_default: int = 32) -> argpar
     ap.add_argument("--timeout", type=float, default=_D.timeout_s, help="process-group timeout in seconds")
     ap.add_argument("--model", default=_D.model,
                     choices=["netresdeep", "resnet50", "resnext50", "seresnet50", "seresnext50", "mobilenet",
-                             "vit"])
+                             "vit", "convnext"])
     ap.add_argument("--bucket-mb", type=float, default=_D.bucket_mb, help="gradient bucket cap (generic DDP path)")
     ap.add_argument("--profile", default=_D.profile, metavar="DIR", help="write torch.profiler traces to DIR")
     ap.add_argument("--check-sync", type=int, default=_D.check_sync, metavar="N",
@@ -422,7 +422,8 @@ def run_eval(model, data, labels, cfg: TrainConfig, kernel: bool = False, ema=No
 
 # --model -> constructor of the generic path: a name of models/resnet50.py, or "module:name" under models/
 RESNET_MODELS = {"resnet50": "resnet50", "resnext50": "resnext50_32x4d", "seresnet50": "se_resnet50",
-                 "seresnext50": "se_resnext50_32x4d", "mobilenet": "mobilenet:mobilenet", "vit": "vit:vit_tiny"}
+                 "seresnext50": "se_resnext50_32x4d", "mobilenet": "mobilenet:mobilenet", "vit": "vit:vit_tiny",
+                 "convnext": "convnext:convnext_tiny"}
 
 
 def generic_model(name: str, num_classes: int = 10):
